@@ -6,13 +6,17 @@ the survey generator (seed 0xC2, 50 % duplicate 2 KiB segments), each chunk
 one independent XCodecEncoder::encode call with its own fresh
 XCodecMemoryCache (XCG_SEM_INDEPENDENT).  A step = one batched encode launch
 over all chunks; inputs, offsets and output slots are resident in HBM before
-the timed region.  Output is bit-exact with the reference encoder: every run
-checks ALL 4096 chunks against the CPU oracle (and the stream-semantics side
-figure all 4096 too).
+the timed region.  A plain run does only that: set up, warm up, time --steps
+steps, write the last step's outputs if --dump-outputs DIR is given, print the
+line.  Everything else is behind --full.  Output is bit-exact with the
+reference encoder: every --full run checks ALL 4096 chunks against the CPU
+oracle (and the stream-semantics side figure all 4096 too), and adds the side
+figures (stream / decode / PCIe / tack loop / C3-C5 configurations / zlib
+stage / CPU baselines) to the line.
 
 Multi-GPU (torchrun, one rank per GPU): every rank encodes its own 4096-chunk
 shard (seed 0xC2 + rank) with no collective in the timed loop -> weak scaling.
-With N > 1 the line also carries `sharded_configs`: BASELINE configs C4 (1 M x
+With N > 1 and --full the line also carries `sharded_configs`: BASELINE configs C4 (1 M x
 4 KiB packets, a private unbounded cache per rank) and C5 (8 GiB in 128 KiB
 calls, "cold cache with xcodec_cache_disk spill": a private XCodecCachePair of
 wanproxy.conf's 128 MiB memory cache over a 1 GiB disk per rank), ONE stream
@@ -46,6 +50,12 @@ def parse():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--chunks', type=int, default=NCHUNKS)
+    ap.add_argument('--full', action='store_true',
+                    help='beside the headline: check every chunk against the CPU oracle and add the side figures '
+                         '(stream / decode / PCIe / tack loop, C3-C5 configurations, zlib stage, CPU baselines; '
+                         'N > 1: sharded_configs).  The --no-* options below trim a --full run')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last step computed to DIR/<name>.npy (dump_outputs)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-seconds', type=float, default=10.0,
                     help='minimum wall of the headline CPU baseline (the reference on T threads)')
@@ -56,7 +66,10 @@ def parse():
     ap.add_argument('--dist-backend', default='nccl',
                     help='torch.distributed backend for N > 1 (nccl = RCCL; gloo rehearses the N > 1 path with '
                          'several ranks sharing one GPU: device = LOCAL_RANK mod the visible GPUs)')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    return args
 
 
 def host_cpus():
@@ -684,6 +697,40 @@ def sharded_configs(world, rank, dev, backend='nccl'):
     return out
 
 
+DUMP_SAMPLE = 64               # chunks of the encoded output written byte for byte (~34 MB as float32)
+
+
+def dump_outputs(path, rank, n, oo, d_out, d_ol, d_st):
+    """--dump-outputs: what the last timed step left in the caller's buffers,
+    as float arrays (every value a small integer, exact in either type) so two
+    builds can be compared file by file; the inputs are seeded, so the same
+    arguments give the same files.
+      out_len.npy     f64 [n]      encoded length of every chunk
+      stats.npy       f64 [n, 4]   the per-chunk stats words (xcgpu.h xcg_encode_batch)
+      out_digest.npy  f64 [n, 2]   of every chunk's encoded bytes b[j]: sum b[j], sum b[j] * (j % 251 + 1)
+      out_sample.npy  f32 [DUMP_SAMPLE, bound]  the encoded bytes of a fixed seeded sample of chunks, each
+                                   row zero past its chunk's length (the whole output as float32 would be ~1 GB)
+      out_sample_chunks.npy  f64 [DUMP_SAMPLE]  which chunks those rows are
+    Ranks above 0 write <name>_rank<r>.npy."""
+    os.makedirs(path, exist_ok=True)
+    sfx = '' if rank == 0 else f'_rank{rank}'
+    ol = d_ol.cpu().numpy().astype(np.int64)
+    outh = d_out.cpu().numpy()
+    st = d_st.cpu().numpy().view(np.uint32).reshape(n, 4)
+    dig = np.zeros((n, 2), np.float64)
+    for i in range(n):
+        b = outh[int(oo[i]):int(oo[i]) + int(ol[i])].astype(np.int64)
+        dig[i, 0] = b.sum()
+        dig[i, 1] = (b * (np.arange(b.size, dtype=np.int64) % 251 + 1)).sum()
+    pick = np.sort(np.random.default_rng(0xD0).choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+    sample = np.zeros((pick.size, 2 * CHUNK + 16), np.float32)      # (a chunk's slot: xcg_encode_bound)
+    for r, i in enumerate(pick):
+        sample[r, :int(ol[i])] = outh[int(oo[i]):int(oo[i]) + int(ol[i])]
+    for name, a in (('out_len', ol.astype(np.float64)), ('stats', st.astype(np.float64)), ('out_digest', dig),
+                    ('out_sample', sample), ('out_sample_chunks', pick.astype(np.float64))):
+        np.save(os.path.join(path, name + sfx + '.npy'), a)
+
+
 def launch_plan(gpus, env):
     """How this invocation runs: ('rank', world) -- one rank of an outer
     launcher (torchrun sets WORLD_SIZE) or the only rank; ('spawn', N) -- no
@@ -769,15 +816,15 @@ def main():
     torch.cuda.synchronize(dev)
     ctx.status()
 
-    # Parity of this run's output: every chunk against the CPU oracle.
-    ol = d_ol.cpu().numpy()
-    outh = d_out.cpu().numpy()
-    exp = oracle_all(data, offs, lens, mode=0)
-    for i in range(n):
-        if outh[int(oo[i]):int(oo[i]) + int(ol[i])].tobytes() != exp[i]:
-            raise SystemExit(f'PARITY FAILURE on chunk {i}')
-    del exp
-    out_bytes = int(ol.sum())
+    if args.full:
+        # Parity of this run's output: every chunk against the CPU oracle.
+        ol = d_ol.cpu().numpy()
+        outh = d_out.cpu().numpy()
+        exp = oracle_all(data, offs, lens, mode=0)
+        for i in range(n):
+            if outh[int(oo[i]):int(oo[i]) + int(ol[i])].tobytes() != exp[i]:
+                raise SystemExit(f'PARITY FAILURE on chunk {i}')
+        del exp, outh
     in_bytes = int(lens.astype(np.int64).sum())
 
     if world > 1:
@@ -796,12 +843,17 @@ def main():
     wall = time.perf_counter() - t0
     kern_ms = ev0.elapsed_time(ev1) / args.steps          # HIP events on the launch stream
     ctx.status()
+    out_bytes = int(d_ol.sum().item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, n, oo, d_out, d_ol, d_st)
 
     extras = {}
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         extras = side_measurements(ctx, data, offs, lens, d_in, d_off, d_len, d_oo, d_out, d_ol, d_st, n, stream, dev,
                                    rank)
-    sharded = sharded_configs(world, rank, dev, args.dist_backend) if world > 1 and not args.no_configs else None
+    sharded = None
+    if args.full and world > 1 and not args.no_configs:
+        sharded = sharded_configs(world, rank, dev, args.dist_backend)
 
     from wanproxy_amd.shard import reduce_run
     red_dev = dev if args.dist_backend == 'nccl' else None
@@ -844,16 +896,17 @@ def main():
         # stream / decode / tack-loop figures and the summary.
         if sharded is not None:
             line['sharded_configs'] = sharded
-        if world == 1 and not args.no_extras and not args.no_configs:
+        if args.full and world == 1 and not args.no_extras and not args.no_configs:
             line['configs'] = other_configs()
-        if world == 1 and not args.no_extras and not args.no_zlib:
+        if args.full and world == 1 and not args.no_extras and not args.no_zlib:
             line['zlib_stage'] = zlib_stage(threads=host_cpus()['threads'])
         if 'host_inclusive' in extras:
             line['host_inclusive'] = extras.pop('host_inclusive')
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(data, offs, lens, args.cpu_seconds)
         line.update(extras)
-        line['summary'] = summary(line)
+        if args.full:
+            line['summary'] = summary(line)
         print(json.dumps(line), flush=True)
     ctx.close()
     if world > 1:

@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 OUT=gpurun_out/prof
 mkdir -p $OUT
-ARGS="--steps ${STEPS:-20} --warmup 2 --no-cpu-baseline ${BENCH_ARGS}"
+ARGS="--full --steps ${STEPS:-20} --warmup 2 --no-cpu-baseline ${BENCH_ARGS}"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 bench.py $ARGS > $OUT/trace.log 2>&1 || exit $?
 PARGS="--steps ${STEPS:-20} --warmup 2 --no-cpu-baseline --no-extras"
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d $OUT/fetch -o run --output-format csv -- python3 bench.py $PARGS > $OUT/fetch.log 2>&1 || exit $?
