@@ -87,6 +87,9 @@ const char *xcg_strerror(int status);
  * every byte literal and 0xF1 (each escaped to two bytes). */
 uint64_t xcg_encode_bound(uint32_t len);
 
+/* A context with an unbounded persistent cache (XCodecMemoryCache(uuid)).
+ * Decode batches on it model every XCodecDecoder::decode behaviour, name reuse
+ * included (see xcg_decode_batch). */
 int xcg_ctx_create(int device, uint32_t flags, xcg_ctx **out);
 /* As xcg_ctx_create with an explicit persistent-cache capacity in 2 KiB
  * segments (XCodecMemoryCache(uuid, limit), xcodec/xcodec_cache.h:277; here
@@ -102,7 +105,10 @@ int xcg_ctx_create_ex(int device, uint32_t flags, uint64_t cache_segments, xcg_c
  * cache.  XCG_ENOTSUP (never a different result): an encode chunk, or a decode
  * call, whose own enters + persistent-entry lookups exceed the limit (encode
  * batches are cut into sub-batches that fit); XCG_SEM_INDEPENDENT with chunks of
- * more than limit * 2048 bytes; BACKREF ops in a decode on a bounded cache. */
+ * more than limit * 2048 bytes; BACKREF ops in a decode on a bounded cache; a
+ * decode batch in which any two EXTRACTs of one hash differ in bytes (name
+ * reuse), or with EXTRACTs of one hash on both sides of its stop point (decode
+ * it in smaller batches). */
 int xcg_ctx_create_bounded(int device, uint32_t flags, uint64_t memory_cache_limit_bytes, xcg_ctx **out);
 /* A context whose persistent cache is wanproxy.conf's XCodecCachePair
  * (xcodec/xcodec_cache.h:140-237, programs/wanproxy/wanproxy.conf:8-26): a
@@ -119,7 +125,9 @@ int xcg_ctx_create_bounded(int device, uint32_t flags, uint64_t memory_cache_lim
  * with XCG_FLAG_OOB / XCG_FLAG_NULLCACHE, or a volume without one index
  * block).  XCG_ENOTSUP (never a different result): a decode batch in which a
  * hash it EXTRACTed leaves both levels before a later op names it (decode it
- * in smaller batches), BACKREF ops.  Decode chunks of a bounded or pair
+ * in smaller batches), BACKREF ops, name reuse inside a decode batch or
+ * EXTRACTs of one hash on both sides of its stop point (as on a bounded
+ * context).  Decode chunks of a bounded or pair
  * context are < 2 MiB each (XCG_EINVAL). */
 int xcg_ctx_create_pair(int device, uint32_t flags, uint64_t memory_cache_limit_bytes, uint64_t disk_bytes,
                         xcg_ctx **out);
@@ -313,6 +321,15 @@ int xcg_encode_call(xcg_ctx *ctx, const uint8_t *h_in, uint32_t len, uint8_t *h_
  * EXTRACTs decoded before the stop point enter the persistent cache
  * (enter / replace, :106-136) and every EXTRACT / REF declares into the
  * decoder's BACKREF window.  Synchronises `stream`.
+ * Name reuse (:106-136: a later EXTRACT of a hash with other bytes replaces
+ * the cache entry) inside a batch, on an unbounded context: a REF yields the
+ * bytes of the latest EXTRACT of its hash before it in the batch, else the
+ * cache's; the window's declares carry the same bytes; the commit takes the
+ * latest EXTRACT before the stop point (EXTRACTs at or after it are not
+ * reached, whether their bytes are equal or not).  Bounded and pair contexts
+ * return XCG_ENOTSUP for such a batch -- whenever any two EXTRACTs of one hash
+ * in it differ in bytes, or a hash has EXTRACTs on both sides of the stop
+ * point -- with the cache, the window and the outputs untouched.
  */
 int xcg_decode_batch(xcg_ctx *ctx, const uint8_t *d_enc, const uint64_t *d_chunk_off, const uint32_t *d_chunk_len,
                      uint32_t n, uint32_t max_chunk_len, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off,
@@ -346,7 +363,7 @@ int xcg_decode_host(xcg_ctx *ctx, const uint8_t *h_enc, uint64_t enc_len, const 
  * launch and one synchronisation on the context's staging and stream, and the
  * XCodecHash of every EXTRACT before the stop comes back in op order
  * (h_extract_hash, *h_nextract; XCG_NO_REFERENCES when not provided: other
- * caches, larger inputs, BACKREF ops -- those take the batch decoder), so a
+ * caches, larger inputs, BACKREF ops, name reuse inside the call -- those take the batch decoder), so a
  * host cache mirror needs no hashing.  XCG_EOVERFLOW if out_cap is too small
  * (*h_out_len = the size needed; nothing is committed). */
 int xcg_decode_call(xcg_ctx *ctx, const uint8_t *h_in, uint32_t len, uint8_t *h_out, uint64_t out_cap,
@@ -532,6 +549,11 @@ uint32_t xcg_debug_set_lds_prefilter_keys(uint32_t keys);
  * the number of segments, and resets them.  Returns the previous setting. */
 int xcg_debug_decode_kernel_timing(int on);
 int xcg_debug_decode_kernel_time(double *step_ms, double *emit_ms, uint32_t *segments);
+/* Diagnostics / tests: the context's last decode batch -- out[0] EXTRACTs of a
+ * hash an earlier-scanned EXTRACT of the batch already had (duplicates), out[1]
+ * hashes whose EXTRACTs differ in bytes (name reuse), out[2] 1 if the batch
+ * took the name-reuse resolver (the sorted occurrence list), else 0. */
+int xcg_debug_decode_reuse(xcg_ctx *ctx, uint64_t out[3]);
 /* Diagnostics / tests: stream batches start either with a parse round against
  * the cache alone, or -- automatically when the context's previous batch
  * declared segments -- from each chunk's 2048-byte tiling (its cold parse),

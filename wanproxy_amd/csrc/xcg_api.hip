@@ -75,6 +75,11 @@ struct XcgDecodeArgs {
   uint32_t maxd;         // EXTRACTs a chunk can hold (bounded: declaration rows per chunk)
   XcgPairState* pair;    // XCodecCachePair (null: not a pair)
   int no_window;         // the BACKREF window is left alone (<LEARN>, single-segment host calls)
+  uint64_t* x_owner;     // name reuse (xcg_decode.hip): slot owners, flags, the duplicate EXTRACT list
+  uint32_t* x_flag;
+  uint32_t* dup_slot;
+  uint64_t* dup_pos;
+  uint32_t dup_cap;
 };
 extern "C" int xcg_launch_pack(const uint8_t*, const uint64_t*, const uint64_t*, uint32_t, uint8_t*, uint64_t*,
                                uint64_t*, hipStream_t);
@@ -169,6 +174,10 @@ struct DecodeScratch {
   uint64_t* x_keys = nullptr;
   uint64_t* x_vals = nullptr;
   uint64_t* x_latest = nullptr;
+  uint64_t* x_owner = nullptr;     // name reuse: the EXTRACT that claimed each slot, the differing-bytes flags,
+  uint32_t* x_flag = nullptr;      // and the later EXTRACTs of a hash (x_cap / 2 >= every EXTRACT of a batch)
+  uint32_t* dup_slot = nullptr;
+  uint64_t* dup_pos = nullptr;
   uint64_t* u_keys = nullptr;      // unknown-hash set (2 * UNKNOWN_CAP)
   uint64_t* unknown = nullptr;
   uint64_t* unknown_pos = nullptr;
@@ -531,6 +540,7 @@ int ensure_scratch(xcg_ctx* c, uint32_t n, uint32_t maxd) {
 void free_dscratch(DecodeScratch& d) {
   (void)hipFree(d.x_keys); (void)hipFree(d.x_vals); (void)hipFree(d.x_latest); (void)hipFree(d.unknown);
   (void)hipFree(d.u_keys);
+  (void)hipFree(d.x_owner); (void)hipFree(d.x_flag); (void)hipFree(d.dup_slot); (void)hipFree(d.dup_pos);
   (void)hipFree(d.unknown_pos); (void)hipFree(d.nunknown); (void)hipFree(d.scratch);
   (void)hipFree(d.chunk_tmp); (void)hipFree(d.d_tail);
   if (d.h_scratch) (void)hipHostFree(d.h_scratch);
@@ -579,6 +589,8 @@ int ensure_dscratch(xcg_ctx* c, uint64_t max_extracts) {
   if (hipMalloc(&d.x_keys, 8ull * cap) != hipSuccess || hipMalloc(&d.x_vals, 8ull * cap) != hipSuccess ||
       hipMalloc(&d.x_latest, 8ull * cap) != hipSuccess || hipMalloc(&d.unknown, 8ull * UNKNOWN_CAP) != hipSuccess ||
       hipMalloc(&d.u_keys, 16ull * UNKNOWN_CAP) != hipSuccess ||
+      hipMalloc(&d.x_owner, 8ull * cap) != hipSuccess || hipMalloc(&d.x_flag, 4ull * cap) != hipSuccess ||
+      hipMalloc(&d.dup_slot, 4ull * (cap / 2)) != hipSuccess || hipMalloc(&d.dup_pos, 8ull * (cap / 2)) != hipSuccess ||
       hipMalloc(&d.unknown_pos, 8ull * UNKNOWN_CAP) != hipSuccess || hipMalloc(&d.nunknown, 16) != hipSuccess ||
       hipMalloc(&d.scratch, 64) != hipSuccess || hipHostMalloc(&d.h_scratch, 128) != hipSuccess) {
     free_dscratch(d);
@@ -1488,7 +1500,8 @@ int decode_batch_impl(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_chunk_
                   c->g.filt, c->g.ftab, c->g.fmask, c->g.gfilt, c->g.gmask, c->ds.x_keys, c->ds.x_vals, c->ds.x_latest, c->ds.x_cap - 1,
                   c->ds.u_keys, c->ds.unknown, c->ds.unknown_pos, c->ds.nunknown, UNKNOWN_CAP, c->ds.scratch, c->ds.h_scratch,
                   c->ds.chunk_tmp, c->ds.d_tail, w->hash, w->seg, w->count, c->bounded ? &c->lru : nullptr,
-                  max_chunk_len / 2050 + 1, c->pair, c->no_window ? 1 : 0};
+                  max_chunk_len / 2050 + 1, c->pair, c->no_window ? 1 : 0, c->ds.x_owner, c->ds.x_flag, c->ds.dup_slot,
+                  c->ds.dup_pos, c->ds.x_cap / 2};
   if (c->pair) {
     const PairGpu G{d_enc, d_chunk_off, nullptr, 0u, c->g.pool, c->g.keys, c->g.vals, c->g.mask, c->g.filt,
                     c->g.ftab, c->g.fmask, c->g.gfilt, c->g.gmask, c->g.nseg, c->d_status};
@@ -1505,7 +1518,7 @@ int decode_batch_impl(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_chunk_
   // status word and the declare count, by async copies into pinned memory
   // (a synchronous 4-byte hipMemcpy costs milliseconds here)
   if (hipMemcpyAsync(c->h_status, c->d_status, 4, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
-      hipMemcpyAsync(c->ds.h_scratch + 7, c->ds.scratch + 5, 8, hipMemcpyDeviceToHost, (hipStream_t)stream) !=
+      hipMemcpyAsync(c->ds.h_scratch + 7, c->ds.scratch + 6, 8, hipMemcpyDeviceToHost, (hipStream_t)stream) !=
           hipSuccess ||
       hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
     return XCG_EHIP;
@@ -1553,6 +1566,13 @@ int xcg_decode_batch(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_chunk_o
     ctx_mark(c, (hipStream_t)stream);
   }
   return rc;
+}
+
+int xcg_debug_decode_reuse(xcg_ctx* c, uint64_t out[3]) {
+  if (!c || !out) return XCG_EINVAL;
+  const uint64_t* h = c->ds.h_scratch;
+  for (int k = 0; k < 3; ++k) out[k] = h ? h[12 + k] : 0;
+  return XCG_OK;
 }
 
 int xcg_window_create(xcg_ctx* c, xcg_window** out) {

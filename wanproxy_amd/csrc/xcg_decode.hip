@@ -19,6 +19,17 @@
 //   commit EXTRACTs before the blocking point enter the cache
 //          (XCodecMemoryCache::enter / replace, :120-136).
 //
+// Name reuse (:106-136, a later EXTRACT of a hash with other bytes replaces the
+// entry, and every later REF reads the new bytes): the scan lists every EXTRACT
+// after a hash's first (`dup`); when there are any, dec_dup_kernel compares
+// each with the hash's first-inserted EXTRACT and flags the hashes whose
+// EXTRACTs differ.  With none flagged every EXTRACT of a hash holds the same
+// bytes and the earliest serves.  Otherwise (unbounded contexts; bounded and
+// pair contexts refuse) the flagged hashes' occurrences are gathered, sorted by
+// (hash, position), and the REUSE instantiations of emit, decl_record and
+// commit resolve a flagged hash by binary search: the latest EXTRACT before
+// the REF (before the stop point, for the commit).
+//
 // BACKREF (:165-181) reads the decoder's XCodecWindow (xcodec/xcodec_window.h):
 // every EXTRACT and resolved REF declares its hash into slot k mod 256 (k =
 // declares made by this decoder so far), emptying the slot that held the same
@@ -36,6 +47,8 @@
 #include <utility>
 #include <vector>
 
+#include <rocprim/device/device_radix_sort.hpp>
+
 #include "xcg_cache.h"
 #include "xcg_args.h"
 
@@ -50,6 +63,17 @@ struct DecParams {
   const uint8_t* pool;
   HashTab x;                   // batch EXTRACT table: hash -> (earliest, latest) packed positions
   uint64_t* x_latest;          // parallel to x.vals: latest position (atomicMax)
+  // ---- name reuse
+  uint64_t* x_owner;           // parallel to x.vals: position of the EXTRACT that claimed the slot
+  uint32_t* x_flag;            // parallel: 1 = the hash's EXTRACTs differ in bytes (valid when the batch has duplicates)
+  uint64_t* dup_ctr;           // duplicates listed so far, minus one (starts at ~0: cleared with the stop positions)
+  uint32_t* dup_slot;          // every EXTRACT after the one that claimed its hash's slot: (slot, position)
+  uint64_t* dup_pos;
+  uint32_t dup_cap;
+  uint32_t* nconf;             // flagged hashes
+  const uint64_t* occ_key;     // (REUSE) EXTRACTs of the flagged hashes sorted by (hash, position), padded
+  const uint64_t* occ_pos;     //   with (~0, ~0) to nocc entries
+  uint32_t nocc;
   uint64_t* out_len;           // scan: tentative decoded length; emit: final
   const uint64_t* out_off;     // emit: exclusive scan of scan's out_len
   uint8_t* out;
@@ -238,9 +262,10 @@ __device__ __forceinline__ uint64_t be64(P p) {
   return h;
 }
 
-// Batch table insert with earliest (vals, atomicMin) and latest (atomicMax).
-__device__ __forceinline__ bool xtab_insert(HashTab t, uint64_t* latest, uint32_t lo, uint32_t hi, uint64_t pos,
-                                            bool& existed) {
+// Batch table insert with earliest (vals, atomicMin) and latest (atomicMax);
+// the EXTRACT that claims the slot records its position as the slot's owner.
+__device__ __forceinline__ bool xtab_insert(HashTab t, uint64_t* latest, uint64_t* owner, uint32_t lo, uint32_t hi,
+                                            uint64_t pos, bool& existed, uint32_t& slot) {
   const uint64_t key = ((uint64_t)hi << 32) | lo;
   uint32_t i = tab_slot(lo, hi, t.mask);
   for (uint32_t n = 0; n <= t.mask; ++n) {
@@ -248,6 +273,8 @@ __device__ __forceinline__ bool xtab_insert(HashTab t, uint64_t* latest, uint32_
                                     (unsigned long long)key);
     if (prev == EMPTY_KEY || prev == key) {
       existed = prev == key;
+      slot = i;
+      if (!existed) owner[i] = pos;
       atomicMin((unsigned long long*)&t.vals[i], (unsigned long long)pos);
       atomicMax((unsigned long long*)&latest[i], (unsigned long long)pos);
       return true;
@@ -305,9 +332,47 @@ __device__ __forceinline__ const uint8_t* ref_source(const DecParams& prm, uint3
   return nullptr;
 }
 
+// Name reuse: the latest EXTRACT of a flagged hash at a position before `here`
+// (~0: none), by binary search in the occurrences sorted by (hash, position).
+__device__ __forceinline__ uint64_t occ_before(const DecParams& prm, uint64_t key, uint64_t here) {
+  uint32_t a = 0, b = prm.nocc;                              // first entry >= (key, here)
+  while (a < b) {
+    const uint32_t mid = a + ((b - a) >> 1);
+    const uint64_t k = prm.occ_key[mid], p = prm.occ_pos[mid];
+    if (k < key || (k == key && p < here)) a = mid + 1;
+    else b = mid;
+  }
+  if (a == 0 || prm.occ_key[a - 1] != key) return ~0ull;
+  return prm.occ_pos[a - 1];
+}
+
+// Per-thread slot of a hash in the batch table (~0: absent).
+__device__ __forceinline__ uint32_t xtab_find_t(const HashTab& t, uint32_t lo, uint32_t hi) {
+  const uint64_t key = ((uint64_t)hi << 32) | lo;
+  uint32_t i = tab_slot(lo, hi, t.mask);
+  for (uint32_t n = 0; n <= t.mask; ++n) {
+    const uint64_t k = t.keys[i];
+    if (k == key) return i;
+    if (k == EMPTY_KEY) break;
+    i = (i + 1) & t.mask;
+  }
+  return ~0u;
+}
+
 // Per-lane REF source (the same rule as ref_source, each lane its own hash).
+// REUSE: a hash whose EXTRACTs differ in bytes resolves to the latest EXTRACT
+// before the REF instead of the earliest (xcodec_decoder.cc:120-136 replaced
+// the entry in between).
+template <bool REUSE>
 __device__ __forceinline__ const uint8_t* ref_source_t(const DecParams& prm, uint32_t lo, uint32_t hi, uint64_t here) {
-  const uint64_t e = tab_lookup_t(prm.x, lo, hi);
+  uint64_t e;
+  if (REUSE) {
+    const uint32_t s = xtab_find_t(prm.x, lo, hi);
+    e = s == ~0u ? ~0ull : prm.x.vals[s];
+    if (s != ~0u && prm.x_flag[s]) e = occ_before(prm, ((uint64_t)hi << 32) | lo, here);
+  } else {
+    e = tab_lookup_t(prm.x, lo, hi);
+  }
   if (e != ~0ull && e < here) return prm.in + prm.chunk_off[e >> 32] + (uint32_t)e;
   const uint64_t gv = tab_lookup_t(prm.g, lo, hi);
   if (g_live(prm, gv, here)) return prm.pool + gv * (uint64_t)SEG;
@@ -364,7 +429,7 @@ __device__ __forceinline__ void copy_segments(uint8_t* dst, const uint8_t* src_l
 
 // ------------------------------------------------------------------ kernels
 
-template <bool EMIT>
+template <bool EMIT, bool REUSE = false>
 __global__ __launch_bounds__(256) void decode_kernel(DecParams prm) {
   const int wv = (int)readfirst(threadIdx.x >> 6);
   const uint32_t chunk = blockIdx.x * 4u + (uint32_t)wv;
@@ -415,11 +480,20 @@ __global__ __launch_bounds__(256) void decode_kernel(DecParams prm) {
         }
       } else {
         const uint2 h = dec_window_hash(seg);
-        bool existed = false;
-        if (l == 0 && !xtab_insert(prm.x, prm.x_latest, readfirst(h.x), readfirst(h.y), spos(chunk, i + 2),
-                                   existed))
-          atomicOr(prm.status, 1 << 10);
-        (void)existed;
+        if (l == 0) {
+          bool existed = false;
+          uint32_t slot = 0;
+          const uint64_t pos = spos(chunk, i + 2);
+          if (!xtab_insert(prm.x, prm.x_latest, prm.x_owner, readfirst(h.x), readfirst(h.y), pos, existed, slot)) {
+            atomicOr(prm.status, 1 << 10);
+          } else if (existed) {                              // a later EXTRACT of the hash: listed for dec_dup_kernel
+            const uint64_t k = atomicAdd((unsigned long long*)prm.dup_ctr, 1ull) + 1ull;
+            if (k < prm.dup_cap) {
+              prm.dup_slot[k] = slot;
+              prm.dup_pos[k] = pos;
+            }
+          }
+        }
       }
       olen += SEG;
       i += 2 + SEG;
@@ -435,7 +509,7 @@ __global__ __launch_bounds__(256) void decode_kernel(DecParams prm) {
       bool stop = false;
       if (EMIT) {
         const uint8_t* src = nullptr;
-        if ((uint32_t)l < r) src = ref_source_t(prm, (uint32_t)h, (uint32_t)(h >> 32), here);
+        if ((uint32_t)l < r) src = ref_source_t<REUSE>(prm, (uint32_t)h, (uint32_t)(h >> 32), here);
         const uint64_t miss = ballot((uint32_t)l < r && src == nullptr);
         if (miss) {                                          // cannot happen: refcheck found all
           r = (uint32_t)__builtin_ctzll(miss);
@@ -484,6 +558,7 @@ __global__ __launch_bounds__(256) void decode_kernel(DecParams prm) {
 // Declare records for batch indices [lo_t, hi_t): full (every declare, when
 // the batch holds BACKREFs) or tail (the 256 before the stop point, for the
 // window update).  One wave per chunk.
+template <bool REUSE>
 __global__ __launch_bounds__(256) void decl_record_kernel(DecParams prm, uint64_t total) {
   const int wv = (int)readfirst(threadIdx.x >> 6);
   const uint32_t chunk = blockIdx.x * 4u + (uint32_t)wv;
@@ -515,7 +590,7 @@ __global__ __launch_bounds__(256) void decl_record_kernel(DecParams prm, uint64_
       const uint32_t r = ref_run(x, i, len, chunk, ~0ull, h, here);
       const uint64_t tl = t + (uint64_t)lane_id();
       if ((uint32_t)lane_id() < r && tl >= lo_t && tl < hi_t) {
-        const uint64_t src = (uint64_t)ref_source_t(prm, (uint32_t)h, (uint32_t)(h >> 32), here);
+        const uint64_t src = (uint64_t)ref_source_t<REUSE>(prm, (uint32_t)h, (uint32_t)(h >> 32), here);
         prm.D[tl - lo_t] = make_uint4((uint32_t)h, (uint32_t)(h >> 32), (uint32_t)src, (uint32_t)(src >> 32));
       }
       t += r;
@@ -680,11 +755,27 @@ __global__ __launch_bounds__(1024) void exclusive_scan_kernel(const uint64_t* le
   if (t == 0) *total = carry;
 }
 
-// Commit: every batch EXTRACT hash whose latest occurrence precedes the
-// blocking point enters the cache (enter, or replace on name reuse).
+// The EXTRACT whose bytes the commit takes for the hash in `slot` (first <
+// blockp): the latest one before the stop point.  Without REUSE every EXTRACT
+// of a hash holds the same bytes, so the earliest stands in for a later one
+// the stream did not reach.  Wave-uniform arguments give a uniform result.
+template <bool REUSE>
+__device__ __forceinline__ uint64_t commit_pos(const DecParams& prm, uint32_t slot, uint64_t first, uint64_t last,
+                                               uint64_t blockp) {
+  if (REUSE && prm.x_flag[slot]) {
+    const uint64_t p = occ_before(prm, prm.x.keys[slot], blockp);
+    return p != ~0ull ? p : first;                           // (first < blockp is listed, so p is found)
+  }
+  return last < blockp ? last : first;
+}
+
+// Commit: every batch EXTRACT hash with an EXTRACT before the blocking point
+// enters the cache with the bytes of the latest such EXTRACT (enter, or
+// replace when the cached bytes differ: name reuse, :120-136).
 // A block takes 256 batch-table slots: one thread per slot decides (enter /
 // replace / skip), new segments are numbered by a block count (one global
 // atomic per block), then the block's waves copy the segments.
+template <bool REUSE>
 __global__ __launch_bounds__(256) void decode_commit_kernel(DecParams prm, uint8_t* pool, uint32_t* nseg,
                                                             uint32_t seg_cap, FiltSet fs) {
   __shared__ uint32_t s_cnt, s_base, s_njob, s_rest;
@@ -697,14 +788,10 @@ __global__ __launch_bounds__(256) void decode_commit_kernel(DecParams prm, uint8
   if (w <= prm.x.mask) {
     key = prm.x.keys[w];
     if (key != EMPTY_KEY) {
-      const uint64_t first = prm.x.vals[w], last = prm.x_latest[w];
+      const uint64_t first = prm.x.vals[w];
       if (first < blockp) {                      // else never reached
-        if (last >= blockp && last != first) {   // several EXTRACTs straddle the block: not modelled
-          atomicOr(prm.status, 1 << 9);
-        } else {
-          gv = tab_lookup_t(prm.g, (uint32_t)key, (uint32_t)(key >> 32));
-          kind = gv != ~0ull ? 2 : 1;
-        }
+        gv = tab_lookup_t(prm.g, (uint32_t)key, (uint32_t)(key >> 32));
+        kind = gv != ~0ull ? 2 : 1;
       }
     }
   }
@@ -747,6 +834,9 @@ __global__ __launch_bounds__(256) void decode_commit_kernel(DecParams prm, uint8
       last[t] = prm.x_latest[slot];
     }
 #pragma unroll
+    for (int t = 0; t < 4; ++t)                    // (last: from here on the EXTRACT the commit takes)
+      last[t] = commit_pos<REUSE>(prm, readfirst(jb[t].x), readfirst64(first[t]), readfirst64(last[t]), blockp);
+#pragma unroll
     for (int t = 0; t < 4; ++t) coff[t] = prm.chunk_off[readfirst64(last[t]) >> 32];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -773,15 +863,10 @@ __global__ __launch_bounds__(256) void decode_commit_kernel(DecParams prm, uint8
   for (uint32_t j = wv; j < njob; j += 4) {
     const uint4 jb = s_job[j];
     const uint32_t slot = readfirst(jb.x), dseg = readfirst(jb.y), jkind = readfirst(jb.z);
-    const uint64_t first = readfirst64(prm.x.vals[slot]), last = readfirst64(prm.x_latest[slot]);
+    const uint64_t first = readfirst64(prm.x.vals[slot]);
+    const uint64_t last = commit_pos<REUSE>(prm, slot, first, readfirst64(prm.x_latest[slot]), blockp);
     if (jkind == 1u && last == first) continue;   // (copied above)
     const uint8_t* src = prm.in + prm.chunk_off[last >> 32] + (uint32_t)last;
-    if (last != first) {
-      // name reuse inside the batch with different bytes would need per-REF
-      // resolution of the latest EXTRACT; the emit pass used the earliest.
-      const uint8_t* s0 = prm.in + prm.chunk_off[first >> 32] + (uint32_t)first;
-      if (!readfirst((uint32_t)dec_equal2048(s0, src)) && lane_id() == 0) atomicOr(prm.status, 1 << 9);
-    }
     uint8_t* dst = pool + (uint64_t)dseg * SEG;
     if (jkind == 1 || !readfirst((uint32_t)dec_equal2048(dst, src))) wave_copy2048(dst, src);   // enter / replace (:130)
   }
@@ -954,12 +1039,61 @@ __global__ __launch_bounds__(256) void dec_replace_kernel(DecParams prm, const u
   }
 }
 
-// Before anything is emitted or committed: batch EXTRACTs of one hash that
-// the batch decoder cannot model -- a second EXTRACT with other bytes (name
-// reuse; REFs between them would need the latest bytes, the emit pass uses the
-// earliest), or EXTRACTs on both sides of the stop point.  Status bit 9 makes
-// xcg_decode_batch refuse the batch (XCG_ENOTSUP) with the cache, window and
-// outputs untouched.  One thread per batch-table slot; the byte compare is rare.
+// Name reuse, detection: one wave per listed duplicate (an EXTRACT of a hash
+// after the one that claimed the hash's slot) compares its 2 KiB with the
+// owner's.  A mismatch flags the slot -- every EXTRACT of an unflagged hash
+// then holds the owner's bytes -- and counts the hash once.  `refuse` (bounded
+// and pair contexts, whose passes do not model name reuse): status bit 9, so
+// xcg_decode_batch declines (XCG_ENOTSUP) before anything is emitted or
+// committed.
+__global__ __launch_bounds__(256) void dec_dup_kernel(DecParams prm, uint32_t ndup, bool refuse) {
+  const uint32_t e = blockIdx.x * 4u + (uint32_t)readfirst(threadIdx.x >> 6);
+  if (e >= ndup) return;
+  const uint32_t slot = readfirst(prm.dup_slot[e]);
+  const uint64_t pos = readfirst64(prm.dup_pos[e]), own = readfirst64(prm.x_owner[slot]);
+  const uint8_t* a = prm.in + prm.chunk_off[own >> 32] + (uint32_t)own;
+  const uint8_t* b = prm.in + prm.chunk_off[pos >> 32] + (uint32_t)pos;
+  if (dec_equal2048(a, b)) return;
+  if (lane_id() == 0) {
+    if (atomicExch(&prm.x_flag[slot], 1u) == 0u) atomicAdd(prm.nconf, 1u);
+    if (refuse) atomicOr(prm.status, 1 << 9);
+  }
+}
+
+// Name reuse, the rare path: every EXTRACT of a flagged hash as (hash,
+// position) -- the slot owners (one thread per table slot), then the listed
+// duplicates (one thread per entry).  `nocc` counts them; the arrays were
+// filled with ~0, which sorts behind every hash.
+__global__ __launch_bounds__(256) void dec_occ_owner_kernel(DecParams prm, uint64_t* okey, uint64_t* opos,
+                                                            uint32_t* nocc, uint32_t cap) {
+  const uint64_t w = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (w > prm.x.mask) return;
+  const uint64_t key = prm.x.keys[w];
+  if (key == EMPTY_KEY || !prm.x_flag[w]) return;
+  const uint32_t k = atomicAdd(nocc, 1u);
+  if (k < cap) {
+    okey[k] = key;
+    opos[k] = prm.x_owner[w];
+  }
+}
+__global__ __launch_bounds__(256) void dec_occ_dup_kernel(DecParams prm, uint32_t ndup, uint64_t* okey, uint64_t* opos,
+                                                          uint32_t* nocc, uint32_t cap) {
+  const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+  if (e >= ndup) return;
+  const uint32_t slot = prm.dup_slot[e];
+  if (!prm.x_flag[slot]) return;
+  const uint32_t k = atomicAdd(nocc, 1u);
+  if (k < cap) {
+    okey[k] = prm.x.keys[slot];
+    opos[k] = prm.dup_pos[e];
+  }
+}
+
+// Bounded and pair contexts, before anything is emitted or committed: a hash
+// with EXTRACTs on both sides of the stop point is not modelled there (status
+// bit 9: XCG_ENOTSUP with the cache, window and outputs untouched; EXTRACTs
+// that differ in bytes were refused by dec_dup_kernel).  One thread per
+// batch-table slot.
 __global__ __launch_bounds__(256) void dec_precheck_kernel(DecParams prm) {
   const uint64_t w = (uint64_t)blockIdx.x * 256u + threadIdx.x;
   if (w > prm.x.mask) return;
@@ -967,14 +1101,7 @@ __global__ __launch_bounds__(256) void dec_precheck_kernel(DecParams prm) {
   if (key == EMPTY_KEY) return;
   const uint64_t first = prm.x.vals[w], last = prm.x_latest[w];
   const uint64_t blockp = min(*prm.block_pos, *prm.berr_pos);
-  if (first >= blockp || last == first) return;
-  bool bad = last >= blockp;
-  if (!bad) {
-    const uint8_t* a = prm.in + prm.chunk_off[first >> 32] + (uint32_t)first;
-    const uint8_t* b = prm.in + prm.chunk_off[last >> 32] + (uint32_t)last;
-    for (uint32_t k = 0; k < SEG && !bad; ++k) bad = a[k] != b[k];
-  }
-  if (bad) atomicOr(prm.status, 1 << 9);
+  if (first < blockp && last != first && last >= blockp) atomicOr(prm.status, 1 << 9);
 }
 
 // Pack per-chunk output slots into one contiguous buffer (one wave per chunk).
@@ -1008,8 +1135,9 @@ __global__ __launch_bounds__(256) void pack_kernel(const uint8_t* src, const uin
 // point and the rest form decode_skim's set), then copy every op before the
 // stop to its output offset, update the BACKREF window (window_slot over the
 // call's declare records) and commit the EXTRACTs before the stop.  Anything
-// the batch decoder refuses or this pass does not cover -- a BACKREF op, name
-// reuse inside the call, EXTRACTs on both sides of the stop, more than
+// this pass does not cover -- a BACKREF op, name reuse inside the call (any
+// EXTRACT whose bytes differ from its hash's earliest), EXTRACTs of one hash
+// on both sides of the stop, more than
 // SD_XSLOTS / 2 EXTRACTs or SD_UMAX unknown hashes -- sets `fallback` before
 // anything is written; the host then takes the batch path.
 constexpr uint32_t SD_XSLOTS = 2048, SD_USLOTS = 4096, SD_UMAX = 2048, SD_EMAX = 1024;
@@ -1057,7 +1185,7 @@ __device__ __forceinline__ void decode_small_body(const SmallDec& a) {
   __shared__ uint4 xin[SD_LDS_IN / 16];
   __shared__ uint16_t xlist[SD_XSLOTS / 2];                  // the occupied EXTRACT slots
   __shared__ uint16_t wcopy[256];                            // window slots that take a new segment
-  __shared__ uint32_t s_nx, s_nw;
+  __shared__ uint32_t s_nx, s_nw, s_ndup;
   const uint32_t t = threadIdx.x, w = t >> 6;
   const int l = lane_id();
   const uint32_t len = a.len;
@@ -1082,7 +1210,7 @@ __device__ __forceinline__ void decode_small_body(const SmallDec& a) {
   for (uint32_t i = t; i < SD_XSLOTS; i += 1024) { xk[i] = EMPTY_KEY; xf[i] = ~0ull; xl[i] = 0; }
   for (uint32_t i = t; i < SD_USLOTS; i += 1024) uk[i] = EMPTY_KEY;
   if (t == 0) {
-    s_nunk = 0; s_fb = 0; s_stop = ~0ull; s_next = 0;
+    s_nunk = 0; s_fb = 0; s_stop = ~0ull; s_next = 0; s_ndup = 0;
     a.res[8 + SD_UMAX + SD_EMAX] = (uint64_t)(uint32_t)*a.status;   // (the paths that return early)
   }
   // (wave 0's walk reads input bytes every wave staged)
@@ -1164,6 +1292,7 @@ __device__ __forceinline__ void decode_small_body(const SmallDec& a) {
         if (prev == EMPTY_KEY || prev == key) {
           atomicMin((unsigned long long*)&xf[i], (unsigned long long)pos);
           atomicMax((unsigned long long*)&xl[i], (unsigned long long)pos);
+          if (prev == key) atomicAdd(&s_ndup, 1u);
           break;
         }
         i = (i + 1) & (SD_XSLOTS - 1);
@@ -1235,16 +1364,25 @@ __device__ __forceinline__ void decode_small_body(const SmallDec& a) {
     if (t == 0) a.res[5] = 1;
     return;
   }
-  // ---- what the batch decoder refuses (dec_precheck_kernel): several EXTRACTs
-  // of one hash before the stop with other bytes, or on both sides of it
+  // ---- what this pass leaves to the batch decoder: an EXTRACT whose bytes
+  // differ from the earliest EXTRACT of its hash (name reuse: REFs between them
+  // resolve by position there; every EXTRACT op is compared, not only the
+  // latest), or EXTRACTs of one hash on both sides of the stop
   const uint32_t nx = s_nx;
-  for (uint32_t q = w; q < nx; q += 16) {
-    const uint32_t i = xlist[q];
-    const uint64_t f = xf[i], z = xl[i];
-    if (f >= stop_pos || z == f) continue;
-    bool bad = z >= stop_pos;
-    if (!bad) bad = !dec_equal2048(x + f, x + z);
-    if (bad && l == 0) atomicOr(&s_fb, 1u);
+  if (s_ndup) {
+    for (uint32_t k = w; k < nops; k += 16) {
+      const uint4 o = a.ops[k];
+      if (readfirst(o.x) != SD_EXT) continue;
+      const uint32_t pos = readfirst(o.y) + 2u;
+      const uint64_t key = readfirst64(a.opv[k]);
+      uint32_t i = mix32((uint32_t)key, (uint32_t)(key >> 32)) & (SD_XSLOTS - 1);
+      for (uint32_t n = 0; n < SD_XSLOTS && xk[i] != key; ++n) i = (i + 1) & (SD_XSLOTS - 1);   // (entered above)
+      const uint64_t f = xf[i];
+      if (f == pos) continue;
+      bool bad = f < stop_pos && pos >= stop_pos;
+      if (!bad) bad = !dec_equal2048(x + f, x + pos);
+      if (bad && l == 0) atomicOr(&s_fb, 1u);
+    }
   }
   __syncthreads();
   SD_STAMP(5);
@@ -1531,10 +1669,11 @@ struct XcgDecodeArgs {
   uint64_t* u_keys;      // unknown-hash set, 2 * unknown_cap slots
   uint64_t* unknown;
   uint64_t* unknown_pos;
-  uint32_t* nunknown;
+  uint32_t* nunknown;    // 4 words: [0] unknown hashes, [1] hashes whose EXTRACTs differ, [2] their occurrences
   uint32_t unknown_cap;
-  uint64_t* scratch;     // [0] total out, [1] REF block, [2] BACKREF error, [3] declares, [4] BACKREFs, [5] t_end
-  uint64_t* h_scratch;   // pinned copy of scratch[0..5], [6] nunknown
+  uint64_t* scratch;     // [0] total out, [1] REF block, [2] BACKREF error, [3] duplicate EXTRACTs - 1, [4] declares,
+                         // [5] BACKREFs, [6] t_end
+  uint64_t* h_scratch;   // pinned copy of scratch[0..5], [6] nunknown | flagged hashes << 32, [12..14] reuse stats
   uint64_t* chunk_tmp;   // 4 * n u64: n_decl, n_bref, decl_base, n_decl_emit
   uint4* d_tail;         // 256 declare records
   uint64_t* win_hash;    // the decoder's BACKREF window
@@ -1544,6 +1683,12 @@ struct XcgDecodeArgs {
   uint32_t maxd;         // EXTRACTs a chunk can hold (bounded: declaration rows per chunk)
   XcgPairState* pair;    // XCodecCachePair (null: not a pair)
   int no_window;         // the BACKREF window is left alone (<LEARN>, single-segment host calls)
+  // name reuse: parallel to x_vals (owner, flag); the duplicate EXTRACT list
+  uint64_t* x_owner;
+  uint32_t* x_flag;
+  uint32_t* dup_slot;
+  uint64_t* dup_pos;
+  uint32_t dup_cap;
 };
 
 // Returns 0, -75 (output too small) or -5.  Outputs: total decoded bytes, the
@@ -1629,7 +1774,15 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
   p.u_mask = 2 * a->unknown_cap - 1;
   p.block_pos = a->scratch + 1;
   p.berr_pos = a->scratch + 2;
-  p.t_end = a->scratch + 5;
+  p.t_end = a->scratch + 6;
+  p.x_owner = a->x_owner;
+  p.x_flag = a->x_flag;
+  p.dup_ctr = a->scratch + 3;
+  p.dup_slot = a->dup_slot;
+  p.dup_pos = a->dup_pos;
+  p.dup_cap = a->dup_cap;
+  p.nconf = a->nunknown + 1;
+  a->h_scratch[12] = a->h_scratch[13] = a->h_scratch[14] = 0;
   p.status = a->status;
   p.n_decl = a->chunk_tmp;
   p.n_bref = a->chunk_tmp + n;
@@ -1643,21 +1796,31 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
   if (hipMemsetAsync(a->x_keys, 0xFF, 8ull * (a->x_mask + 1), stream) != hipSuccess ||
       hipMemsetAsync(a->x_vals, 0xFF, 8ull * (a->x_mask + 1), stream) != hipSuccess ||
       hipMemsetAsync(a->x_latest, 0, 8ull * (a->x_mask + 1), stream) != hipSuccess ||
-      hipMemsetAsync(a->scratch + 1, 0xFF, 16, stream) != hipSuccess ||
-      hipMemsetAsync(a->nunknown, 0, 4, stream) != hipSuccess ||
+      hipMemsetAsync(a->scratch + 1, 0xFF, 24, stream) != hipSuccess ||      // (stop positions, duplicate count - 1)
+      hipMemsetAsync(a->nunknown, 0, 16, stream) != hipSuccess ||
       hipMemsetAsync(a->u_keys, 0xFF, 16ull * a->unknown_cap, stream) != hipSuccess)
     return -5;
   // scan, then number the declares
   hipLaunchKernelGGL(decode_kernel<false>, grid, block, 0, stream, p);
   hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, stream, (const uint64_t*)p.n_decl,
-                     (uint64_t*)p.decl_base, n, a->scratch + 3);
+                     (uint64_t*)p.decl_base, n, a->scratch + 4);
   hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, stream, (const uint64_t*)p.n_bref,
-                     p.n_decl_emit, n, a->scratch + 4);          // (n_decl_emit: scratch output here)
+                     p.n_decl_emit, n, a->scratch + 5);          // (n_decl_emit: scratch output here)
   seg1.end();
-  if (hipMemcpyAsync(a->h_scratch + 3, a->scratch + 3, 16, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+  if (hipMemcpyAsync(a->h_scratch + 3, a->scratch + 3, 24, hipMemcpyDeviceToHost, stream) != hipSuccess ||
       hipStreamSynchronize(stream) != hipSuccess)
     return -5;
-  const uint64_t ndecl = a->h_scratch[3], nbref = a->h_scratch[4];
+  const uint64_t ndup = a->h_scratch[3] + 1u, ndecl = a->h_scratch[4], nbref = a->h_scratch[5];
+  // Duplicate EXTRACTs (rare; none in an encoder's stream on a fresh cache):
+  // compare each with its hash's owner and flag the hashes whose bytes differ.
+  // The count of flagged hashes comes back with the sizing pass's readback.
+  if (ndup > a->dup_cap) return -5;                  // (the list holds every EXTRACT the batch can have)
+  a->h_scratch[12] = ndup;
+  if (ndup) {
+    if (hipMemsetAsync(a->x_flag, 0, 4ull * (a->x_mask + 1), stream) != hipSuccess) return -5;
+    hipLaunchKernelGGL(dec_dup_kernel, dim3((unsigned)((ndup + 3) / 4)), dim3(256), 0, stream, p, (uint32_t)ndup,
+                       a->lru != nullptr || a->pair != nullptr);
+  }
   // Bounded cache: classify every op against the eviction times until they
   // agree (xcg_lru.hip); the passes below then see the cache as it evolves.
   uint8_t* lru_mem = nullptr;
@@ -1770,26 +1933,29 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
     p.D = dfull;
     p.D_lo = 0;
     p.D_tail = false;
-    hipLaunchKernelGGL(decl_record_kernel, grid, block, 0, stream, p, ndecl);
+    hipLaunchKernelGGL(decl_record_kernel<false>, grid, block, 0, stream, p, ndecl);
   }
   DecTimer seg2(stream, &g_dt_step);
   hipLaunchKernelGGL(decode_refcheck_kernel, grid, block, 0, stream, p);
   if (nbref > 0) hipLaunchKernelGGL(decode_brefcheck_kernel, grid, block, 0, stream, p);
   hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, stream, (const uint64_t*)a->out_len, a->out_off,
                      n, a->scratch);
-  hipLaunchKernelGGL(dec_precheck_kernel, dim3((unsigned)(((uint64_t)a->x_mask + 256) / 256)), dim3(256), 0, stream,
-                     p);
+  if (a->lru || a->pair)
+    hipLaunchKernelGGL(dec_precheck_kernel, dim3((unsigned)(((uint64_t)a->x_mask + 256) / 256)), dim3(256), 0, stream,
+                       p);
   seg2.end();
   a->h_scratch[10] = 0;
   if (hipMemcpyAsync(a->h_scratch, a->scratch, 24, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-      hipMemcpyAsync(a->h_scratch + 6, a->nunknown, 4, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+      hipMemcpyAsync(a->h_scratch + 6, a->nunknown, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
       hipMemcpyAsync(a->h_scratch + 10, a->status, 4, hipMemcpyDeviceToHost, stream) != hipSuccess ||
       hipStreamSynchronize(stream) != hipSuccess) {
     if (dfull) (void)hipFreeAsync(dfull, stream);
     return -5;
   }
+  const uint32_t nconf = (uint32_t)(a->h_scratch[6] >> 32);
+  a->h_scratch[13] = nconf;
   if (a->h_scratch[10] & (1u << 9)) {
-    // refused before any output, cache or window change (dec_precheck_kernel)
+    // refused before any output, cache or window change (dec_dup_kernel, dec_precheck_kernel)
     a->h_scratch[11] = a->h_scratch[10] & ~(uint64_t)(1u << 9);
     (void)hipMemcpyAsync(a->status, a->h_scratch + 11, 4, hipMemcpyHostToDevice, stream);
     (void)hipStreamSynchronize(stream);
@@ -1808,6 +1974,46 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
     if (pair_mem) (void)hipFreeAsync(pair_mem, stream);
     return -75;
   }
+  // Name reuse (hashes whose EXTRACTs differ; unbounded contexts only get
+  // here): their occurrences sorted by (hash, position) -- a stable sort by
+  // position, then by hash -- for the REUSE kernels' binary search.
+  uint8_t* occ_mem = nullptr;
+  if (nconf) {
+    const uint32_t m = (uint32_t)ndup + nconf;       // owners of the flagged hashes + at most every duplicate
+    uint64_t *k0 = nullptr, *k1 = nullptr, *v0 = nullptr, *v1 = nullptr;
+    size_t tmp1 = 0, tmp2 = 0;
+    if (rocprim::radix_sort_pairs(nullptr, tmp1, v0, v1, k0, k1, m, 0, 64, stream) != hipSuccess ||
+        rocprim::radix_sort_pairs(nullptr, tmp2, k1, k0, v1, v0, m, 0, 64, stream) != hipSuccess ||
+        hipMallocAsync((void**)&occ_mem, 32ull * m + 256 + (tmp1 > tmp2 ? tmp1 : tmp2), stream) != hipSuccess) {
+      if (dfull) (void)hipFreeAsync(dfull, stream);
+      return -5;
+    }
+    k0 = (uint64_t*)occ_mem; k1 = k0 + m; v0 = k1 + m; v1 = v0 + m;
+    void* tmp = (void*)(((uintptr_t)(v1 + m) + 255) & ~(uintptr_t)255);
+    uint32_t* nocc = a->nunknown + 2;
+    if (hipMemsetAsync(occ_mem, 0xFF, 32ull * m, stream) != hipSuccess) {
+      (void)hipFreeAsync(occ_mem, stream);
+      if (dfull) (void)hipFreeAsync(dfull, stream);
+      return -5;
+    }
+    hipLaunchKernelGGL(dec_occ_owner_kernel, dim3((unsigned)(((uint64_t)a->x_mask + 256) / 256)), dim3(256), 0, stream,
+                       p, k0, v0, nocc, m);
+    hipLaunchKernelGGL(dec_occ_dup_kernel, dim3((unsigned)((ndup + 255) / 256)), dim3(256), 0, stream, p, (uint32_t)ndup,
+                       k0, v0, nocc, m);
+    if (rocprim::radix_sort_pairs(tmp, tmp1, v0, v1, k0, k1, m, 0, 64, stream) != hipSuccess ||
+        rocprim::radix_sort_pairs(tmp, tmp2, k1, k0, v1, v0, m, 0, 64, stream) != hipSuccess) {
+      (void)hipFreeAsync(occ_mem, stream);
+      if (dfull) (void)hipFreeAsync(dfull, stream);
+      return -5;
+    }
+    p.occ_key = k0;
+    p.occ_pos = v0;
+    p.nocc = m;
+    a->h_scratch[14] = 1;
+    // (BACKREFs: the records made before the sizing pass carry the earliest
+    // EXTRACT as a flagged REF's source; the hashes, all the checks read, stand)
+    if (dfull) hipLaunchKernelGGL(decl_record_kernel<true>, grid, block, 0, stream, p, ndecl);
+  }
   DecTimer seg3(stream, &g_dt_step), emit(stream, &g_dt_emit);
   // No stop point: the declares end at ndecl, so the window's tail is known
   // now and the emit pass records it (no second walk over the ops).
@@ -1817,7 +2023,8 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
     p.tail_hi = ndecl;
     p.tail_lo = ndecl > 256u ? ndecl - 256u : 0u;
   }
-  hipLaunchKernelGGL(decode_kernel<true>, grid, block, 0, stream, p);
+  if (nconf) hipLaunchKernelGGL((decode_kernel<true, true>), grid, block, 0, stream, p);
+  else hipLaunchKernelGGL((decode_kernel<true, false>), grid, block, 0, stream, p);
   emit.end();
   p.tail_D = nullptr;
   hipLaunchKernelGGL(decode_tend_kernel, dim3(1), dim3(1), 0, stream, p, ndecl);
@@ -1825,7 +2032,10 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
     if (!dfull) {
       p.D = a->d_tail;
       p.D_tail = true;
-      if (!fuse_tail) hipLaunchKernelGGL(decl_record_kernel, grid, block, 0, stream, p, ndecl);
+      if (!fuse_tail) {
+        if (nconf) hipLaunchKernelGGL(decl_record_kernel<true>, grid, block, 0, stream, p, ndecl);
+        else hipLaunchKernelGGL(decl_record_kernel<false>, grid, block, 0, stream, p, ndecl);
+      }
     }
     hipLaunchKernelGGL(window_update_kernel, dim3(64), dim3(256), 0, stream, p);
   }
@@ -1846,10 +2056,16 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
     if (crc) return crc;
   } else {
     const uint64_t slots = (uint64_t)a->x_mask + 1;
-    hipLaunchKernelGGL(decode_commit_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, stream, p,
-                       a->pool, a->nseg, a->seg_cap, FiltSet{a->g_filt, a->g_ftab, a->fmask, a->g_gfilt, a->gmask});
+    const FiltSet fs{a->g_filt, a->g_ftab, a->fmask, a->g_gfilt, a->gmask};
+    if (nconf)
+      hipLaunchKernelGGL(decode_commit_kernel<true>, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, stream, p,
+                         a->pool, a->nseg, a->seg_cap, fs);
+    else
+      hipLaunchKernelGGL(decode_commit_kernel<false>, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, stream, p,
+                         a->pool, a->nseg, a->seg_cap, fs);
     seg3.end();
   }
+  if (occ_mem) (void)hipFreeAsync(occ_mem, stream);
   if (dfull) (void)hipFreeAsync(dfull, stream);
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }

@@ -176,6 +176,8 @@ def lib():
     L.xcg_debug_decode_kernel_timing.restype = C.c_int
     L.xcg_debug_decode_kernel_time.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
     L.xcg_debug_decode_kernel_time.restype = C.c_int
+    L.xcg_debug_decode_reuse.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.xcg_debug_decode_reuse.restype = C.c_int
     L.xcg_debug_set_screen.argtypes = [C.c_int]
     L.xcg_debug_set_screen.restype = C.c_int
     L.xcg_debug_screen_counts.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -332,6 +334,13 @@ class Context:
         a, b = C.c_uint64(), C.c_uint64()
         _check(lib().xcg_debug_restart_counts(self.h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
+
+    def decode_reuse_stats(self):
+        """(duplicate EXTRACTs, hashes whose EXTRACTs differ in bytes, whether
+        the name-reuse resolver ran) of this context's last decode batch."""
+        st = (C.c_uint64 * 3)()
+        _check(lib().xcg_debug_decode_reuse(self.h, st))
+        return int(st[0]), int(st[1]), bool(st[2])
 
     def cache_clear(self):
         _check(lib().xcg_cache_clear(self.h))
