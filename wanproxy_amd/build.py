@@ -5,6 +5,7 @@ Each source compiles to its own object in parallel (objects are reused while
 they are newer than the source and every header), then one link."""
 from __future__ import annotations
 
+import glob
 import os
 import subprocess
 from concurrent.futures import ThreadPoolExecutor
@@ -12,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRCS = ['csrc/xcg_api.hip', 'csrc/xcg_encode.hip', 'csrc/xcg_decode.hip', 'csrc/xcg_hash.hip', 'csrc/xcg_lru.hip',
         'csrc/xcg_pair.hip', 'csrc/xcg_pipe.cpp', 'csrc/xcg_deflate.hip', 'csrc/xcg_inflate.hip']
-HDRS = ['csrc/xcg_device.h', 'csrc/xcg_cache.h', 'csrc/xcg_args.h', '../include/xcgpu.h']
+HDRS = sorted(glob.glob(os.path.join(HERE, 'csrc', '*.h'))) + ['../include/xcgpu.h']   # every object depends on all
 OUT = os.path.join(HERE, 'libxcgpu.so')
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall'] + os.environ.get('XCG_EXTRA_FLAGS', '').split()

@@ -23,89 +23,14 @@
 
 #include "../../include/xcgpu.h"
 #include "xcg_args.h"
-
-extern "C" int xcg_launch_encode_independent(const uint8_t*, const uint64_t*, const uint32_t*, uint32_t, uint32_t,
-                                             uint32_t, uint8_t*, const uint64_t*, uint64_t*, uint32_t*, int32_t*,
-                                             hipStream_t);
-extern "C" int xcg_launch_window_hashes(const uint8_t*, uint64_t, uint64_t*, hipStream_t);
-
-
-extern "C" int xcg_launch_segment_hashes(const uint8_t*, uint64_t, uint64_t*, hipStream_t);
-
-struct XcgDecodeArgs {
-  const uint8_t* in;
-  const uint64_t* chunk_off;
-  const uint32_t* chunk_len;
-  uint32_t n;
-  uint8_t* out;
-  uint64_t out_cap;
-  uint64_t* out_off;
-  uint64_t* out_len;
-  int32_t* chunk_status;
-  uint64_t* consumed;
-  int32_t* status;
-  uint64_t* g_keys;
-  uint64_t* g_vals;
-  uint32_t g_mask;
-  uint8_t* pool;
-  uint32_t* nseg;
-  uint32_t seg_cap;
-  uint32_t* g_filt;
-  uint32_t* g_ftab;
-  uint32_t fmask;
-  uint32_t* g_gfilt;
-  uint32_t gmask;
-  uint64_t* x_keys;
-  uint64_t* x_vals;
-  uint64_t* x_latest;
-  uint32_t x_mask;
-  uint64_t* u_keys;
-  uint64_t* unknown;
-  uint64_t* unknown_pos;
-  uint32_t* nunknown;
-  uint32_t unknown_cap;
-  uint64_t* scratch;
-  uint64_t* h_scratch;
-  uint64_t* chunk_tmp;
-  uint4* d_tail;
-  uint64_t* win_hash;
-  uint8_t* win_seg;
-  uint64_t win_count;
-  XcgLruState* lru;      // bounded cache (null: unbounded)
-  uint32_t maxd;         // EXTRACTs a chunk can hold (bounded: declaration rows per chunk)
-  XcgPairState* pair;    // XCodecCachePair (null: not a pair)
-  int no_window;         // the BACKREF window is left alone (<LEARN>, single-segment host calls)
-  uint64_t* x_owner;     // name reuse (xcg_decode.hip): slot owners, flags, the duplicate EXTRACT list
-  uint32_t* x_flag;
-  uint32_t* dup_slot;
-  uint64_t* dup_pos;
-  uint32_t dup_cap;
-};
-extern "C" int xcg_launch_pack(const uint8_t*, const uint64_t*, const uint64_t*, uint32_t, uint8_t*, uint64_t*,
-                               uint64_t*, hipStream_t);
-extern "C" int xcg_launch_cache_lookup(uint64_t*, uint64_t*, uint32_t, const uint8_t*, uint64_t, uint8_t*, int32_t*,
-                                       hipStream_t);
-extern "C" int xcg_launch_cache_enter(uint64_t*, uint64_t*, uint32_t, uint8_t*, uint32_t*, uint32_t, uint32_t*,
-                                      uint32_t*, uint32_t, uint32_t*, uint32_t, uint64_t, const uint8_t*, int, int32_t*,
-                                      hipStream_t);
-extern "C" int xcg_launch_decode(const XcgDecodeArgs*, uint64_t*, uint64_t*, uint64_t*, uint32_t*, hipStream_t);
+#include "xcg_cache.h"
 
 // The persistent segment cache of a context: XCodecMemoryCache's
 // hash_map<Tag64, BufferSegment*> (xcodec/xcodec_cache.h:270) as an
 // open-addressed table in HBM plus a segment pool, and the two lane-probe
-// filters over it (see xcg_cache.h).
-struct GpuCache {
-  uint64_t* keys = nullptr;
-  uint64_t* vals = nullptr;
-  uint32_t mask = 0;
-  uint8_t* pool = nullptr;
-  uint32_t seg_cap = 0;
-  uint32_t* nseg = nullptr;     // device counter
-  uint32_t* filt = nullptr;     // FILT_WORDS
-  uint32_t* ftab = nullptr;     // fbuckets * 4
-  uint32_t fmask = 0;
-  uint32_t* gfilt = nullptr;    // global lane filter: gmask + 1 words (~1 per segment)
-  uint32_t gmask = 0;
+// filters over it (see xcg_cache.h): the view the drivers get, and who owns
+// the pool.
+struct GpuCache : XcgCacheView {
   bool pool_borrowed = false;   // (a pair front's pool: owned by its XcgPairState)
 };
 
@@ -289,8 +214,13 @@ struct DeviceGuard {
   }
 };
 
-constexpr uint32_t FILT_WORDS = (1u << 19) / 32;   // xcg_cache.h FILT_LOG2
-constexpr uint32_t PREFIX_FILTERS = 16;             // xcg_cache.h: slices of a round's LDS filter
+using xcg::FILT_WORDS;
+using xcg::PREFIX_FILTERS;
+
+// A driver's return code (0 or a negative errno-like value) as an ABI status.
+int status_of(int rc) {
+  return rc == 0 ? XCG_OK : (rc == -75 ? XCG_EOVERFLOW : (rc == -95 ? XCG_ENOTSUP : XCG_EHIP));
+}
 
 // The context's last call was enqueued on last_mark; done_ev is recorded
 // behind it only when another stream or a host wait needs it.  Recording it
@@ -946,15 +876,13 @@ int host_seg_call(xcg_ctx* c, uint64_t hash, const uint8_t* in_seg, uint8_t* out
   }
   rc = XCG_OK;
   if (mode == 0) {   // lookup
-    if (xcg_launch_cache_lookup(c->g.keys, c->g.vals, c->g.mask, c->g.pool, hash, d_seg, d_res, nullptr) != 0 ||
+    if (xcg_launch_cache_lookup(&c->g, hash, d_seg, d_res, nullptr) != 0 ||
         hipMemcpy(res, d_res, 4, hipMemcpyDeviceToHost) != hipSuccess ||
         (*res && hipMemcpy(out_seg, d_seg, XCG_SEGMENT_LENGTH, hipMemcpyDeviceToHost) != hipSuccess))
       rc = XCG_EHIP;
   } else {           // enter (1) / replace (2)
     if (hipMemcpy(d_seg, in_seg, XCG_SEGMENT_LENGTH, hipMemcpyHostToDevice) != hipSuccess ||
-        xcg_launch_cache_enter(c->g.keys, c->g.vals, c->g.mask, c->g.pool, c->g.nseg, c->g.seg_cap, c->g.filt,
-                               c->g.ftab, c->g.fmask, c->g.gfilt, c->g.gmask, hash, d_seg, mode == 2, d_res,
-                               nullptr) != 0 ||
+        xcg_launch_cache_enter(&c->g, hash, d_seg, mode == 2, d_res, nullptr) != 0 ||
         hipMemcpy(res, d_res, 4, hipMemcpyDeviceToHost) != hipSuccess)
       rc = XCG_EHIP;
   }
@@ -982,7 +910,7 @@ int lru_host_call(xcg_ctx* c, uint64_t hash, const uint8_t* in_seg, uint8_t* out
   int32_t* d_res = (int32_t*)(m + 4096);
   rc = XCG_OK;
   do {
-    if (xcg_launch_cache_lookup(c->g.keys, c->g.vals, c->g.mask, c->g.pool, hash, d_old, d_res, nullptr) != 0 ||
+    if (xcg_launch_cache_lookup(&c->g, hash, d_old, d_res, nullptr) != 0 ||
         hipMemcpy(found, d_res, 4, hipMemcpyDeviceToHost) != hipSuccess) {
       rc = XCG_EHIP;
       break;
@@ -998,8 +926,7 @@ int lru_host_call(xcg_ctx* c, uint64_t hash, const uint8_t* in_seg, uint8_t* out
     }
     int32_t res = 0;
     if (enter && *found &&                          // replace (the table entry stays)
-        (xcg_launch_cache_enter(c->g.keys, c->g.vals, c->g.mask, c->g.pool, c->g.nseg, c->g.seg_cap, c->g.filt,
-                                c->g.ftab, c->g.fmask, c->g.gfilt, c->g.gmask, hash, d_new, 1, d_res, nullptr) != 0 ||
+        (xcg_launch_cache_enter(&c->g, hash, d_new, 1, d_res, nullptr) != 0 ||
          hipMemcpy(&res, d_res, 4, hipMemcpyDeviceToHost) != hipSuccess)) {
       rc = XCG_EHIP;
       break;
@@ -1032,10 +959,14 @@ int lru_host_call(xcg_ctx* c, uint64_t hash, const uint8_t* in_seg, uint8_t* out
     L.enter_base = (uint32_t*)at(h.enter_base);
     L.evslot = (uint32_t*)at(h.evslot);
     L.evtime = (uint64_t*)at(h.evtime);
-    const LruBatch b{1u, d_new, (const uint64_t*)at(&h.chunk_off), at(h.decl), (const uint32_t*)at(&h.ndecl), 1u,
-                     at(h.ev), (const uint32_t*)at(&h.nev), 1u, 0, (uint32_t*)at(&h.need), c->g.keys, c->g.vals,
-                     c->g.mask, c->g.pool, c->g.nseg, c->g.filt, c->g.ftab, c->g.fmask, c->g.gfilt, c->g.gmask,
-                     c->d_status, 1u};
+    LruBatch b{};
+    b.n = 1; b.in = d_new; b.chunk_off = (const uint64_t*)at(&h.chunk_off);
+    b.decl = at(h.decl); b.ndecl = (const uint32_t*)at(&h.ndecl); b.maxd = 1;
+    b.ev = at(h.ev); b.nev = (const uint32_t*)at(&h.nev); b.maxe = 1;
+    b.need = (uint32_t*)at(&h.need);
+    b.g = c->g;
+    b.status = c->d_status;
+    b.ev_bound = 1;
     if (xcg_lru_times(&b, &L, nullptr) != 0 || xcg_lru_commit(&b, &L, nullptr) != 0 ||
         hipStreamSynchronize(nullptr) != hipSuccess)
       rc = XCG_EHIP;
@@ -1226,6 +1157,51 @@ int xcg_ctx_status(xcg_ctx* c) {
 }  // extern "C"
 
 namespace {
+// A stream batch's driver arguments from the context (its cache and scratch,
+// ensure_cache / ensure_scratch done) and the call: the same for the plain,
+// bounded and pair drivers.
+XcgStreamArgs stream_args(xcg_ctx* c, const uint8_t* d_in, const uint64_t* d_chunk_off, const uint32_t* d_chunk_len,
+                          uint32_t n, uint32_t maxd, uint8_t* d_out, const uint64_t* d_out_off, uint64_t* d_out_len,
+                          uint32_t* d_stats) {
+  const BatchScratch& b = c->bs;
+  XcgStreamArgs a{};
+  a.in = d_in; a.chunk_off = d_chunk_off; a.chunk_len = d_chunk_len; a.n = n;
+  a.flags = c->flags;
+  a.out = d_out; a.out_off = d_out_off; a.out_len = d_out_len;
+  a.stats = d_stats;
+  a.status = c->d_status;
+  a.g = c->g;
+  a.b_keys = b.b_keys; a.b_vals = b.b_vals; a.b_mask = b.b_mask;
+  a.r_filt = b.r_filt; a.r_ftab = b.r_ftab; a.r_gfilt = b.r_gfilt;
+  a.decl = b.decl; a.ndecl = b.ndecl; a.maxd = maxd;
+  a.changed = b.changed; a.h_changed = b.h_changed;
+  a.bcount = b.bcount;
+  a.b2_keys = b.b2_keys; a.b2_vals = b.b2_vals;
+  a.r_keys = b.r_keys; a.r_vals = b.r_vals; a.r_mask = b.r_mask;
+  a.hits = b.hits; a.nhits = b.nhits; a.maxh = b.maxh;
+  a.need = b.need;
+  a.vflags = b.vflags; a.h_vflags = b.h_vflags;
+  // Seed the rounds with the chunks' 2048-byte tilings instead of a parse
+  // round 0 when the last batch declared segments (cold / growing caches);
+  // a warm cache's all-REF batches keep round 0, which then is all they need.
+  const int mode = __atomic_load_n(&g_stream_seed, __ATOMIC_RELAXED);
+  a.seed = mode < 0 ? (c->seed_next ? 1 : 0) : mode;
+  a.a_keys = b.a_keys;
+  a.a_vals = b.a_vals;
+  a.a_bits = getenv("XCG_NO_APROBE") ? nullptr : b.a_bits;
+  a.flags_ev = c->flags_ev;
+  a.s_fold = b.s_fold; a.s_work = b.s_work; a.s_info = b.s_info; a.s_rows = b.s_rows;
+  a.s_qcnt = b.s_qcnt; a.s_qkeys = b.s_qkeys;
+  if (c->pair || c->bounded) {
+    a.ev = b.ev; a.nev = b.nev; a.maxe = b.maxe;
+    a.eo = b.eo; a.bad_t = b.bad_t; a.bad_hi = b.bad_hi; a.bslot = b.bslot; a.b_count = b.b_count;
+    a.b_slots = b.b_slots; a.b_ev = b.b_ev; a.b_eo = b.b_eo; a.b_hits = b.b_hits; a.b_cnt = b.b_cnt;
+    a.b_out = b.b_out; a.b_stride = b.b_stride; a.splice = b.splice;
+    a.restart = getenv("XCG_NO_RESTART") ? 0 : 1;
+  }
+  return a;
+}
+
 int encode_batch_impl(xcg_ctx* c, int semantics, const uint8_t* d_in, const uint64_t* d_chunk_off,
                       const uint32_t* d_chunk_len, uint32_t n, uint32_t max_chunk_len, uint8_t* d_out,
                       const uint64_t* d_out_off, uint64_t* d_out_len, uint32_t* d_stats, void* stream) {
@@ -1244,62 +1220,24 @@ int encode_batch_impl(xcg_ctx* c, int semantics, const uint8_t* d_in, const uint
     if (rc == XCG_OK) rc = ensure_scratch(c, n, maxd);
     if (rc != XCG_OK) return rc;
     c->bs.last_maxd = maxd;
-    XcgStreamArgs a{d_in, d_chunk_off, d_chunk_len, n, c->flags, d_out, d_out_off, d_out_len, d_stats,
-                    c->d_status, c->g.keys, c->g.vals, c->g.mask, c->g.pool, c->g.nseg, c->g.seg_cap,
-                    c->g.filt, c->g.ftab, c->g.fmask, c->bs.b_keys, c->bs.b_vals, c->bs.b_mask,
-                    c->bs.r_filt, c->bs.r_ftab, c->bs.decl, c->bs.ndecl, maxd, c->bs.changed, c->bs.h_changed,
-                    c->g.gfilt, c->bs.r_gfilt, c->g.gmask, c->bs.bcount, c->bs.b2_keys, c->bs.b2_vals,
-                    c->bs.r_keys, c->bs.r_vals, c->bs.r_mask, c->bs.hits, c->bs.nhits, c->bs.maxh, c->bs.need,
-                    c->bs.vflags, c->bs.h_vflags, 0, nullptr, nullptr, nullptr, nullptr, 0u, 0, 0, 0};
-    // Seed the rounds with the chunks' 2048-byte tilings instead of a parse
-    // round 0 when the last batch declared segments (cold / growing caches);
-    // a warm cache's all-REF batches keep round 0, which then is all they need.
-    const int mode = __atomic_load_n(&g_stream_seed, __ATOMIC_RELAXED);
-    a.seed = mode < 0 ? (c->seed_next ? 1 : 0) : mode;
+    XcgStreamArgs a = stream_args(c, d_in, d_chunk_off, d_chunk_len, n, maxd, d_out, d_out_off, d_out_len, d_stats);
     uint32_t decls = ~0u;
     a.decls_out = &decls;
     int rounds = 0;
-    a.a_keys = c->bs.a_keys;
-    a.a_vals = c->bs.a_vals;
-    a.a_bits = getenv("XCG_NO_APROBE") ? nullptr : c->bs.a_bits;
-    a.flags_ev = c->flags_ev;
-    a.s_fold = c->bs.s_fold;
-    a.s_work = c->bs.s_work;
-    a.s_info = c->bs.s_info;
-    a.s_rows = c->bs.s_rows;
-    a.s_qcnt = c->bs.s_qcnt;
-    a.s_qkeys = c->bs.s_qkeys;
-    if (c->pair || c->bounded) {
-      BatchScratch& b = c->bs;
-      a.eo = b.eo; a.bad_t = b.bad_t; a.bad_hi = b.bad_hi; a.bslot = b.bslot; a.b_count = b.b_count;
-      a.b_slots = b.b_slots; a.b_ev = b.b_ev; a.b_eo = b.b_eo; a.b_hits = b.b_hits; a.b_cnt = b.b_cnt;
-      a.b_out = b.b_out; a.b_stride = b.b_stride; a.splice = b.splice;
-      a.restart = getenv("XCG_NO_RESTART") ? 0 : 1;
-    }
     if (c->pair) {
-      a.ev = c->bs.ev;
-      a.nev = c->bs.nev;
-      a.maxe = c->bs.maxe;
       rc = xcg_pair_encode_stream(&a, c->pair, &rounds, (hipStream_t)stream);
-      c->last_rounds = rounds;
-      return rc == 0 ? XCG_OK : (rc == -75 ? XCG_EOVERFLOW : (rc == -95 ? XCG_ENOTSUP : XCG_EHIP));
-    }
-    if (c->bounded) {
-      a.ev = c->bs.ev;
-      a.nev = c->bs.nev;
-      a.maxe = c->bs.maxe;
+    } else if (c->bounded) {
       c->lru.ev_base = c->bs.ev_base;
       c->lru.enter_base = c->bs.enter_base;
       c->lru.evslot = c->bs.ev_slot;
       c->lru.evtime = c->bs.ev_time;
       rc = xcg_lru_encode_stream(&a, &c->lru, &rounds, (hipStream_t)stream);
-      c->last_rounds = rounds;
-      return rc == 0 ? XCG_OK : (rc == -75 ? XCG_EOVERFLOW : (rc == -95 ? XCG_ENOTSUP : XCG_EHIP));
+    } else {
+      rc = xcg_launch_encode_stream(&a, &rounds, (hipStream_t)stream);
+      if (decls != ~0u) c->seed_next = decls > 0;
     }
-    rc = xcg_launch_encode_stream(&a, &rounds, (hipStream_t)stream);
-    if (decls != ~0u) c->seed_next = decls > 0;
     c->last_rounds = rounds;
-    return rc == 0 ? XCG_OK : (rc == -75 ? XCG_EOVERFLOW : XCG_EHIP);
+    return status_of(rc);   // (the plain driver never returns -95: 0, -5 or -75)
   }
   // A fresh bounded cache per chunk evicts nothing while the chunk's
   // declarations fit the limit (at most max_chunk_len / 2048 of them).
@@ -1307,7 +1245,7 @@ int encode_batch_impl(xcg_ctx* c, int semantics, const uint8_t* d_in, const uint
   if (c->pair && max_chunk_len / XCG_SEGMENT_LENGTH > c->pair_C) return XCG_ENOTSUP;
   int rc = xcg_launch_encode_independent(d_in, d_chunk_off, d_chunk_len, n, max_chunk_len, c->flags, d_out,
                                          d_out_off, d_out_len, d_stats, c->d_status, (hipStream_t)stream);
-  return rc == 0 ? XCG_OK : (rc == -22 ? XCG_EINVAL : XCG_EHIP);
+  return rc == -22 ? XCG_EINVAL : status_of(rc);   // (the independent driver returns 0, -22 or -5)
 }
 }  // namespace
 
@@ -1472,6 +1410,35 @@ int xcg_encode_call(xcg_ctx* c, const uint8_t* h_in, uint32_t len, uint8_t* h_ou
 }  // extern "C"
 
 namespace {
+// A decode batch's driver arguments from the context (its cache, scratch and
+// current window, all allocated) and the call.
+XcgDecodeArgs decode_args(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_chunk_off, const uint32_t* d_chunk_len,
+                          uint32_t n, uint32_t max_chunk_len, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off,
+                          uint64_t* d_out_len, int32_t* d_chunk_status, uint64_t* d_consumed) {
+  const DecodeScratch& d = c->ds;
+  const xcg_window* w = c->cur_win;
+  XcgDecodeArgs a{};
+  a.in = d_enc; a.chunk_off = d_chunk_off; a.chunk_len = d_chunk_len; a.n = n;
+  a.out = d_out; a.out_cap = out_cap; a.out_off = d_out_off; a.out_len = d_out_len;
+  a.chunk_status = d_chunk_status; a.consumed = d_consumed;
+  a.status = c->d_status;
+  a.g = c->g;
+  a.x_keys = d.x_keys; a.x_vals = d.x_vals; a.x_latest = d.x_latest; a.x_mask = d.x_cap - 1;
+  a.u_keys = d.u_keys; a.unknown = d.unknown; a.unknown_pos = d.unknown_pos; a.nunknown = d.nunknown;
+  a.unknown_cap = UNKNOWN_CAP;
+  a.scratch = d.scratch; a.h_scratch = d.h_scratch;
+  a.chunk_tmp = d.chunk_tmp;
+  a.d_tail = d.d_tail;
+  a.win_hash = w->hash; a.win_seg = w->seg; a.win_count = w->count;
+  a.lru = c->bounded ? &c->lru : nullptr;
+  a.maxd = max_chunk_len / 2050 + 1;
+  a.pair = c->pair;
+  a.no_window = c->no_window ? 1 : 0;
+  a.x_owner = d.x_owner; a.x_flag = d.x_flag; a.dup_slot = d.dup_slot; a.dup_pos = d.dup_pos;
+  a.dup_cap = d.x_cap / 2;
+  return a;
+}
+
 int decode_batch_impl(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_chunk_off, const uint32_t* d_chunk_len,
                       uint32_t n, uint32_t max_chunk_len, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off,
                       uint64_t* d_out_len, int32_t* d_chunk_status, uint64_t* d_consumed, uint64_t* h_unknown,
@@ -1495,25 +1462,20 @@ int decode_batch_impl(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_chunk_
   }
   if (rc != XCG_OK) return rc;
   xcg_window* w = c->cur_win;
-  XcgDecodeArgs a{d_enc, d_chunk_off, d_chunk_len, n, d_out, out_cap, d_out_off, d_out_len, d_chunk_status,
-                  d_consumed, c->d_status, c->g.keys, c->g.vals, c->g.mask, c->g.pool, c->g.nseg, c->g.seg_cap,
-                  c->g.filt, c->g.ftab, c->g.fmask, c->g.gfilt, c->g.gmask, c->ds.x_keys, c->ds.x_vals, c->ds.x_latest, c->ds.x_cap - 1,
-                  c->ds.u_keys, c->ds.unknown, c->ds.unknown_pos, c->ds.nunknown, UNKNOWN_CAP, c->ds.scratch, c->ds.h_scratch,
-                  c->ds.chunk_tmp, c->ds.d_tail, w->hash, w->seg, w->count, c->bounded ? &c->lru : nullptr,
-                  max_chunk_len / 2050 + 1, c->pair, c->no_window ? 1 : 0, c->ds.x_owner, c->ds.x_flag, c->ds.dup_slot,
-                  c->ds.dup_pos, c->ds.x_cap / 2};
+  const XcgDecodeArgs a = decode_args(c, d_enc, d_chunk_off, d_chunk_len, n, max_chunk_len, d_out, out_cap, d_out_off,
+                                      d_out_len, d_chunk_status, d_consumed);
   if (c->pair) {
-    const PairGpu G{d_enc, d_chunk_off, nullptr, 0u, c->g.pool, c->g.keys, c->g.vals, c->g.mask, c->g.filt,
-                    c->g.ftab, c->g.fmask, c->g.gfilt, c->g.gmask, c->g.nseg, c->d_status};
+    PairGpu G{};
+    G.in = d_enc; G.chunk_off = d_chunk_off;
+    G.g = c->g;
+    G.status = c->d_status;
     if (xcg_pair_sync(c->pair, &G, (hipStream_t)stream)) return XCG_EHIP;
   }
   uint64_t total = 0, blockp = 0, berr = 0;
   uint32_t nunk = 0;
   const int lrc = xcg_launch_decode(&a, &total, &blockp, &berr, &nunk, (hipStream_t)stream);
   if (h_total_out) *h_total_out = total;
-  if (lrc == -75) return XCG_EOVERFLOW;
-  if (lrc == -95) return XCG_ENOTSUP;
-  if (lrc != 0) return XCG_EHIP;
+  if (lrc != 0) return status_of(lrc);
   if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return XCG_EHIP;
   // status word and the declare count, by async copies into pinned memory
   // (a synchronous 4-byte hipMemcpy costs milliseconds here)
@@ -1644,15 +1606,6 @@ int xcg_decode_host(xcg_ctx* c, const uint8_t* h_enc, uint64_t enc_len, const ui
 
 }  // extern "C"
 
-extern "C" int xcg_launch_decode_small(const uint8_t*, uint32_t, uint64_t*, uint64_t*, uint32_t, uint8_t*, uint32_t*,
-                                       uint32_t, uint32_t*, uint32_t*, uint32_t, uint32_t*, uint32_t, int32_t*, void*,
-                                       uint32_t, uint8_t*, uint64_t, uint64_t*, uint8_t*, uint64_t, uint64_t*,
-                                       uint64_t*, uint32_t*, uint32_t, hipStream_t);
-extern "C" uint64_t xcg_decode_small_scratch(uint32_t ops_cap);
-extern "C" uint32_t xcg_decode_small_lds_in(void);
-extern "C" uint32_t xcg_decode_small_res_words(void);
-extern "C" uint32_t xcg_decode_small_phases(void);
-
 // Diagnostics: with XCG_DECODE_PHASES set, every one-launch decode() records
 // clock stamps at its phase boundaries (decode_small_kernel); the sums of the
 // phase durations and the call count come back through
@@ -1744,10 +1697,9 @@ int decode_call_zc(xcg_ctx* c, const uint8_t* h_in, uint32_t len, uint8_t* h_out
   const hipStream_t st = c->call_st;
   ctx_order(c, st);
   xcg_window* w = c->cur_win;
-  if (xcg_launch_decode_small(dzb + 256, len, c->g.keys, c->g.vals, c->g.mask, c->g.pool, c->g.nseg, c->g.seg_cap,
-                              c->g.filt, c->g.ftab, c->g.fmask, c->g.gfilt, c->g.gmask, c->d_status, c->stage_d,
-                              ops_cap, dzb + 256 + inb, out_cap, w->hash, w->seg, w->count,
-                              (uint64_t*)(dzb + 256 + inb + outb), nullptr, (uint32_t*)dzb, seq, st) != 0)
+  if (xcg_launch_decode_small(dzb + 256, len, &c->g, c->d_status, c->stage_d, ops_cap, dzb + 256 + inb, out_cap,
+                              w->hash, w->seg, w->count, (uint64_t*)(dzb + 256 + inb + outb), nullptr, (uint32_t*)dzb,
+                              seq, st) != 0)
     return XCG_EHIP;
   ctx_mark(c, st);
   // Spin (with a pause per poll, so a sibling hyperthread keeps its share) for
@@ -1832,11 +1784,9 @@ int xcg_decode_call(xcg_ctx* c, const uint8_t* h_in, uint32_t len, uint8_t* h_ou
     ctx_order(c, st);
     xcg_window* w = c->cur_win;
     if (hipMemcpyAsync(dm, hm, len, hipMemcpyHostToDevice, st) != hipSuccess ||
-        xcg_launch_decode_small(dm, len, c->g.keys, c->g.vals, c->g.mask, c->g.pool, c->g.nseg, c->g.seg_cap,
-                                c->g.filt, c->g.ftab, c->g.fmask, c->g.gfilt, c->g.gmask, c->d_status,
-                                dm + inb + outb + resb, ops_cap, dm + inb, out_cap, w->hash, w->seg, w->count,
-                                d_res, timb ? (uint64_t*)(dm + inb + outb + resb + scr) : nullptr, nullptr, 0u,
-                                st) != 0 ||
+        xcg_launch_decode_small(dm, len, &c->g, c->d_status, dm + inb + outb + resb, ops_cap, dm + inb, out_cap,
+                                w->hash, w->seg, w->count, d_res,
+                                timb ? (uint64_t*)(dm + inb + outb + resb + scr) : nullptr, nullptr, 0u, st) != 0 ||
         hipMemcpyAsync(h_o, dm + inb, outb + 8ull * rw, hipMemcpyDeviceToHost, st) != hipSuccess)
       return XCG_EHIP;
     ctx_mark(c, st);

@@ -1,9 +1,36 @@
-// Arguments of the stream-semantics encode driver (xcg_launch_encode_stream),
-// shared by xcg_api.hip (the caller) and xcg_lru.hip (the bounded-cache pass).
+// The library's internal interface: every struct and every extern "C" function
+// that crosses translation units inside libxcgpu (the host ABI layer
+// xcg_api.hip, xcg_pipe.cpp and the kernel drivers xcg_encode / xcg_decode /
+// xcg_lru / xcg_pair / xcg_hash).  The file that defines one of these functions
+// and every file that calls it include this header, so a prototype that drifts
+// is a compile error.  Plain data only: xcg_pipe.cpp compiles it as host C++.
+//
+// The argument structs are filled from `T a{};` (everything zero / null) by
+// named member assignment, never by a positional initialiser list.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+struct xcg_ctx;
+
+// Device view of a context's persistent segment cache (layout: xcg_cache.h):
+// the exact table, the segment pool and the lane-probe filters over the table.
+struct XcgCacheView {
+  uint64_t* keys = nullptr;
+  uint64_t* vals = nullptr;
+  uint32_t mask = 0;
+  uint8_t* pool = nullptr;
+  uint32_t seg_cap = 0;
+  uint32_t* nseg = nullptr;     // device counter
+  uint32_t* filt = nullptr;     // FILT_WORDS
+  uint32_t* ftab = nullptr;     // fbuckets * 4
+  uint32_t fmask = 0;
+  uint32_t* gfilt = nullptr;    // global lane filter: gmask + 1 words (~1 per segment)
+  uint32_t gmask = 0;
+};
+
+// Arguments of the stream-semantics encode driver (xcg_launch_encode_stream),
+// and of the bounded-cache and pair passes around it.
 struct XcgStreamArgs {
   const uint8_t* in;
   const uint64_t* chunk_off;
@@ -15,16 +42,7 @@ struct XcgStreamArgs {
   uint64_t* out_len;
   uint32_t* stats;
   int32_t* status;
-  // persistent cache
-  uint64_t* g_keys;
-  uint64_t* g_vals;
-  uint32_t g_mask;
-  uint8_t* pool;
-  uint32_t* nseg;
-  uint32_t seg_cap;
-  uint32_t* g_filt;
-  uint32_t* g_ftab;
-  uint32_t fmask;
+  XcgCacheView g;        // persistent cache
   // batch scratch
   uint64_t* b_keys;
   uint64_t* b_vals;
@@ -36,9 +54,7 @@ struct XcgStreamArgs {
   uint32_t maxd;
   uint32_t* changed;
   uint32_t* h_changed;   // pinned host word
-  uint32_t* g_gfilt;     // global lane filters: the cache's and the round's copy
-  uint32_t* r_gfilt;
-  uint32_t gmask;
+  uint32_t* r_gfilt;     // the round's copy of the cache's global lane filter
   uint32_t* bcount;      // [64]
   // verification: a second batch table (tables alternate between rounds), the
   // changed-hash table, per-chunk batch hits, flags
@@ -92,16 +108,16 @@ struct XcgStreamArgs {
   // the quiet-chunk screen (small chunks): the 128 KiB LDS fold of the round's
   // global lane filter, and the work list of chunks it sends to the parse
   // ([0] count, [1..n] chunks); null: no screen
-  uint32_t* s_fold = nullptr;
-  uint32_t* s_work = nullptr;
-  uint32_t* s_info = nullptr;    // [n] the screen's verdict per chunk
-  void* s_rows = nullptr;        // [n * 4] uint4: its staged rows
-  uint32_t* s_qcnt = nullptr;    // [n] and [n * 1024]: the windows it queues for the probe
-  uint32_t* s_qkeys = nullptr;
+  uint32_t* s_fold;
+  uint32_t* s_work;
+  uint32_t* s_info;    // [n] the screen's verdict per chunk
+  void* s_rows;        // [n * 4] uint4: its staged rows
+  uint32_t* s_qcnt;    // [n] and [n * 1024]: the windows it queues for the probe
+  uint32_t* s_qkeys;
   // (bounded cache) called behind each Jacobi verification, before the host
   // reads its flags: queues work gated on vflags[1] == 0 (the round converged)
-  int (*post_verify)(void* user, const uint32_t* vbusy, hipStream_t st) = nullptr;
-  void* post_user = nullptr;
+  int (*post_verify)(void* user, const uint32_t* vbusy, hipStream_t st);
+  void* post_user;
 };
 
 // (a)-probe sizes: at most A_LIMIT newly visible hashes per verification (more:
@@ -150,16 +166,7 @@ struct LruBatch {
   uint32_t maxe;
   int dense;
   uint32_t* need;         // (encoder) chunks with an inconsistent lookup; may be scratch
-  uint64_t* g_keys;
-  uint64_t* g_vals;
-  uint32_t g_mask;
-  uint8_t* pool;
-  uint32_t* nseg;
-  uint32_t* g_filt;
-  uint32_t* g_ftab;
-  uint32_t fmask;
-  uint32_t* g_gfilt;
-  uint32_t gmask;
+  XcgCacheView g;
   int32_t* status;
   uint64_t ev_bound;      // upper bound of the batch's references (sizes the scans)
   uint32_t* bad_t;        // (encoder, optional) per chunk earliest / latest contradicted lookup time
@@ -178,16 +185,7 @@ struct PairGpu {
   const uint64_t* chunk_off;
   const void* decl;       // uint4 rows: decl[c * maxd + d].z = the segment's offset in chunk c
   uint32_t maxd;
-  uint8_t* pool;
-  uint64_t* g_keys;
-  uint64_t* g_vals;
-  uint32_t g_mask;
-  uint32_t* g_filt;
-  uint32_t* g_ftab;
-  uint32_t fmask;
-  uint32_t* g_gfilt;
-  uint32_t gmask;
-  uint32_t* nseg;
+  XcgCacheView g;
   int32_t* status;
 };
 extern "C" int xcg_disk_state_create(uint64_t disk_bytes, uint32_t flags, XcgDiskState** out);
@@ -220,9 +218,82 @@ extern "C" int xcg_pair_decode_pass(XcgPairState* P, const PairGpu* G, const voi
 extern "C" uint8_t* xcg_pair_state_pool(const XcgPairState* P);
 extern "C" int xcg_pair_decode_commit(XcgPairState* P, const PairGpu* G, hipStream_t st);
 
+
+// Arguments of the batch decode driver (xcg_launch_decode).
+struct XcgDecodeArgs {
+  const uint8_t* in;
+  const uint64_t* chunk_off;
+  const uint32_t* chunk_len;
+  uint32_t n;
+  uint8_t* out;
+  uint64_t out_cap;
+  uint64_t* out_off;
+  uint64_t* out_len;
+  int32_t* chunk_status;
+  uint64_t* consumed;
+  int32_t* status;
+  XcgCacheView g;        // persistent cache
+  uint64_t* x_keys;
+  uint64_t* x_vals;
+  uint64_t* x_latest;
+  uint32_t x_mask;
+  uint64_t* u_keys;      // unknown-hash set, 2 * unknown_cap slots
+  uint64_t* unknown;
+  uint64_t* unknown_pos;
+  uint32_t* nunknown;    // 4 words: [0] unknown hashes, [1] hashes whose EXTRACTs differ, [2] their occurrences
+  uint32_t unknown_cap;
+  uint64_t* scratch;     // [0] total out, [1] REF block, [2] BACKREF error, [3] duplicate EXTRACTs - 1, [4] declares,
+                         // [5] BACKREFs, [6] t_end
+  uint64_t* h_scratch;   // pinned copy of scratch[0..5], [6] nunknown | flagged hashes << 32, [12..14] reuse stats
+  uint64_t* chunk_tmp;   // 4 * n u64: n_decl, n_bref, decl_base, n_decl_emit
+  uint4* d_tail;         // 256 declare records
+  uint64_t* win_hash;    // the decoder's BACKREF window
+  uint8_t* win_seg;
+  uint64_t win_count;
+  XcgLruState* lru;      // bounded cache (null: unbounded)
+  uint32_t maxd;         // EXTRACTs a chunk can hold (bounded: declaration rows per chunk)
+  XcgPairState* pair;    // XCodecCachePair (null: not a pair)
+  int no_window;         // the BACKREF window is left alone (<LEARN>, single-segment host calls)
+  // name reuse: parallel to x_vals (owner, flag); the duplicate EXTRACT list
+  uint64_t* x_owner;
+  uint32_t* x_flag;
+  uint32_t* dup_slot;
+  uint64_t* dup_pos;
+  uint32_t dup_cap;
+};
+
 extern "C" int xcg_launch_encode_stream(const XcgStreamArgs* a, int* rounds_out, hipStream_t stream);
 extern "C" int xcg_lru_encode_stream(const XcgStreamArgs* a, XcgLruState* L, int* rounds_out, hipStream_t st);
 extern "C" int xcg_lru_times(const LruBatch* b, XcgLruState* L, hipStream_t st);
 extern "C" int xcg_lru_commit(const LruBatch* b, XcgLruState* L, hipStream_t st);
 extern "C" int xcg_lru_reset_times(XcgLruState* L, hipStream_t st);
 extern "C" int xcg_launch_seed_tiling(const XcgStreamArgs* a, hipStream_t stream);
+extern "C" int xcg_launch_encode_independent(const uint8_t* d_in, const uint64_t* d_chunk_off,
+                                             const uint32_t* d_chunk_len, uint32_t n, uint32_t max_chunk_len,
+                                             uint32_t flags, uint8_t* d_out, const uint64_t* d_out_off,
+                                             uint64_t* d_out_len, uint32_t* d_stats, int32_t* d_status,
+                                             hipStream_t stream);
+
+extern "C" int xcg_launch_window_hashes(const uint8_t* d_x, uint64_t len, uint64_t* d_hash, hipStream_t stream);
+extern "C" int xcg_launch_segment_hashes(const uint8_t* d_x, uint64_t len, uint64_t* d_hash, hipStream_t stream);
+
+extern "C" int xcg_launch_cache_lookup(const XcgCacheView* g, uint64_t key, uint8_t* seg_out, int32_t* found,
+                                       hipStream_t s);
+extern "C" int xcg_launch_cache_enter(const XcgCacheView* g, uint64_t key, const uint8_t* seg, int replace_only,
+                                      int32_t* result, hipStream_t s);
+extern "C" int xcg_launch_pack(const uint8_t* src, const uint64_t* src_off, const uint64_t* len, uint32_t n,
+                               uint8_t* dst, uint64_t* dst_off, uint64_t* d_total, hipStream_t stream);
+extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, uint64_t* block_pos_out,
+                                 uint64_t* berr_pos_out, uint32_t* nunknown_out, hipStream_t stream);
+extern "C" int xcg_launch_decode_small(const uint8_t* in, uint32_t len, const XcgCacheView* g, int32_t* status,
+                                       void* scratch, uint32_t ops_cap, uint8_t* out, uint64_t out_cap,
+                                       uint64_t* win_hash, uint8_t* win_seg, uint64_t win_count, uint64_t* res,
+                                       uint64_t* tim, uint32_t* flag, uint32_t seq, hipStream_t stream);
+extern "C" uint64_t xcg_decode_small_scratch(uint32_t ops_cap);
+extern "C" uint32_t xcg_decode_small_res_words(void);
+extern "C" uint32_t xcg_decode_small_phases(void);
+extern "C" uint32_t xcg_decode_small_lds_in(void);
+
+// (xcg_api.hip for xcg_pipe.cpp) a connecting pipe takes and drops its registry context
+extern "C" void xcg_registry_hold(xcg_ctx* c);
+extern "C" void xcg_registry_release(xcg_ctx* c);

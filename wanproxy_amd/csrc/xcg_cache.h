@@ -13,6 +13,7 @@
 //                    per 2^18 segments) stays in an XCD's L2
 //   filt[FILT_BITS / 32] u32  the bitmap a workgroup loads into LDS (bit K mod 2^19)
 #pragma once
+#include "xcg_args.h"
 #include "xcg_device.h"
 
 namespace xcg {
@@ -63,6 +64,10 @@ struct FiltSet {
   uint32_t* gfilt;    // (gmask + 1): the global lane filter (large caches)
   uint32_t gmask;
 };
+
+// The persistent cache's table and filters (host side: what the drivers hand the kernels).
+inline HashTab tab_of(const XcgCacheView& g) { return HashTab{g.keys, g.vals, g.mask}; }
+inline FiltSet filters_of(const XcgCacheView& g) { return FiltSet{g.filt, g.ftab, g.fmask, g.gfilt, g.gmask}; }
 
 __device__ __forceinline__ uint32_t mix32(uint32_t a, uint32_t b) {
   uint32_t h = a * 0x9E3779B1u ^ (b + 0x7F4A7C15u) * 0x85EBCA77u;

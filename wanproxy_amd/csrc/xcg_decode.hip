@@ -1613,19 +1613,17 @@ __global__ __launch_bounds__(64) void cache_enter_kernel(HashTab g, uint8_t* poo
 
 }  // namespace xcg
 
-extern "C" int xcg_launch_cache_lookup(uint64_t* keys, uint64_t* vals, uint32_t mask, const uint8_t* pool, uint64_t key,
-                                       uint8_t* seg_out, int32_t* found, hipStream_t s) {
-  hipLaunchKernelGGL(xcg::cache_lookup_kernel, dim3(1), dim3(64), 0, s, xcg::HashTab{keys, vals, mask}, pool, key,
+extern "C" int xcg_launch_cache_lookup(const XcgCacheView* g, uint64_t key, uint8_t* seg_out, int32_t* found,
+                                       hipStream_t s) {
+  hipLaunchKernelGGL(xcg::cache_lookup_kernel, dim3(1), dim3(64), 0, s, xcg::tab_of(*g), (const uint8_t*)g->pool, key,
                      seg_out, found);
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
-extern "C" int xcg_launch_cache_enter(uint64_t* keys, uint64_t* vals, uint32_t mask, uint8_t* pool, uint32_t* nseg,
-                                      uint32_t seg_cap, uint32_t* filt, uint32_t* ftab, uint32_t fmask, uint32_t* gfilt,
-                                      uint32_t gmask, uint64_t key, const uint8_t* seg, int replace_only,
+extern "C" int xcg_launch_cache_enter(const XcgCacheView* g, uint64_t key, const uint8_t* seg, int replace_only,
                                       int32_t* result, hipStream_t s) {
-  hipLaunchKernelGGL(xcg::cache_enter_kernel, dim3(1), dim3(64), 0, s, xcg::HashTab{keys, vals, mask}, pool, nseg,
-                     seg_cap, xcg::FiltSet{filt, ftab, fmask, gfilt, gmask}, key, seg, replace_only, result);
+  hipLaunchKernelGGL(xcg::cache_enter_kernel, dim3(1), dim3(64), 0, s, xcg::tab_of(*g), g->pool, g->nseg, g->seg_cap,
+                     xcg::filters_of(*g), key, seg, replace_only, result);
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
@@ -1638,58 +1636,6 @@ extern "C" int xcg_launch_pack(const uint8_t* src, const uint64_t* src_off, cons
                      dst, n);
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
-
-struct XcgDecodeArgs {
-  const uint8_t* in;
-  const uint64_t* chunk_off;
-  const uint32_t* chunk_len;
-  uint32_t n;
-  uint8_t* out;
-  uint64_t out_cap;
-  uint64_t* out_off;
-  uint64_t* out_len;
-  int32_t* chunk_status;
-  uint64_t* consumed;
-  int32_t* status;
-  uint64_t* g_keys;
-  uint64_t* g_vals;
-  uint32_t g_mask;
-  uint8_t* pool;
-  uint32_t* nseg;
-  uint32_t seg_cap;
-  uint32_t* g_filt;
-  uint32_t* g_ftab;
-  uint32_t fmask;
-  uint32_t* g_gfilt;
-  uint32_t gmask;
-  uint64_t* x_keys;
-  uint64_t* x_vals;
-  uint64_t* x_latest;
-  uint32_t x_mask;
-  uint64_t* u_keys;      // unknown-hash set, 2 * unknown_cap slots
-  uint64_t* unknown;
-  uint64_t* unknown_pos;
-  uint32_t* nunknown;    // 4 words: [0] unknown hashes, [1] hashes whose EXTRACTs differ, [2] their occurrences
-  uint32_t unknown_cap;
-  uint64_t* scratch;     // [0] total out, [1] REF block, [2] BACKREF error, [3] duplicate EXTRACTs - 1, [4] declares,
-                         // [5] BACKREFs, [6] t_end
-  uint64_t* h_scratch;   // pinned copy of scratch[0..5], [6] nunknown | flagged hashes << 32, [12..14] reuse stats
-  uint64_t* chunk_tmp;   // 4 * n u64: n_decl, n_bref, decl_base, n_decl_emit
-  uint4* d_tail;         // 256 declare records
-  uint64_t* win_hash;    // the decoder's BACKREF window
-  uint8_t* win_seg;
-  uint64_t win_count;
-  XcgLruState* lru;      // bounded cache (null: unbounded)
-  uint32_t maxd;         // EXTRACTs a chunk can hold (bounded: declaration rows per chunk)
-  XcgPairState* pair;    // XCodecCachePair (null: not a pair)
-  int no_window;         // the BACKREF window is left alone (<LEARN>, single-segment host calls)
-  // name reuse: parallel to x_vals (owner, flag); the duplicate EXTRACT list
-  uint64_t* x_owner;
-  uint32_t* x_flag;
-  uint32_t* dup_slot;
-  uint64_t* dup_pos;
-  uint32_t dup_cap;
-};
 
 // Returns 0, -75 (output too small) or -5.  Outputs: total decoded bytes, the
 // REF block and BACKREF error positions (~0 = none), unknown-REF count.
@@ -1732,6 +1678,17 @@ double dt_sum(std::vector<std::pair<hipEvent_t, hipEvent_t>>& v) {
   v.clear();
   return tot;
 }
+
+// What the pair's passes touch of a decode batch: its input, the
+// classification's declaration rows and the cache.
+PairGpu pair_gpu(const XcgDecodeArgs* a, const void* rows) {
+  PairGpu G{};
+  G.in = a->in; G.chunk_off = a->chunk_off;
+  G.decl = rows; G.maxd = a->maxd;
+  G.g = a->g;
+  G.status = a->status;
+  return G;
+}
 }  // namespace
 extern "C" int xcg_debug_decode_kernel_timing(int on) {
   std::lock_guard<std::mutex> g(g_dt_mu);
@@ -1757,8 +1714,8 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
   p.chunk_off = a->chunk_off;
   p.chunk_len = a->chunk_len;
   p.n = n;
-  p.g = HashTab{a->g_keys, a->g_vals, a->g_mask};
-  p.pool = a->pool;
+  p.g = tab_of(a->g);
+  p.pool = a->g.pool;
   p.x = HashTab{a->x_keys, a->x_vals, a->x_mask};
   p.x_latest = a->x_latest;
   p.out_len = a->out_len;
@@ -1846,9 +1803,13 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
     L->enter_base = L->ev_base + (n + 1);
     uint64_t* blk = (uint64_t*)(((uintptr_t)(L->enter_base + n + 1) + 15) & ~(uintptr_t)15);
     uint32_t* changes = (uint32_t*)(blk + 1);
-    lb = LruBatch{n, a->in, a->chunk_off, drow, nd32, a->maxd, evs, nev32, 0xFFFFFFFFu, 1, need,
-                  a->g_keys, a->g_vals, a->g_mask, a->pool, a->nseg, a->g_filt, a->g_ftab, a->fmask,
-                  a->g_gfilt, a->gmask, a->status, m};
+    lb.n = n; lb.in = a->in; lb.chunk_off = a->chunk_off;
+    lb.decl = drow; lb.ndecl = nd32; lb.maxd = a->maxd;
+    lb.ev = evs; lb.nev = nev32; lb.maxe = 0xFFFFFFFFu; lb.dense = 1;
+    lb.need = need;
+    lb.g = a->g;
+    lb.status = a->status;
+    lb.ev_bound = m;
     auto fail = [&](int rc) {
       (void)hipFreeAsync(lru_mem, stream);
       return rc;
@@ -1913,8 +1874,7 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
                          a->maxd, blockp, blk, changes, 1);
       if (hipMemcpyAsync(a->h_scratch + 8, blk, 8, hipMemcpyDeviceToHost, stream) != hipSuccess) return fail(-5);
       int same = 0;
-      const PairGpu G{a->in, a->chunk_off, prow, a->maxd, a->pool, a->g_keys, a->g_vals, a->g_mask,
-                      a->g_filt, a->g_ftab, a->fmask, a->g_gfilt, a->gmask, a->nseg, a->status};
+      const PairGpu G = pair_gpu(a, prow);
       const int prc = xcg_pair_decode_pass(a->pair, &G, evs, p.decl_base, p.n_decl, n, ndecl, a->maxd, &same, stream);
       if (prc) return fail(prc);
       const uint64_t nb = a->h_scratch[8];
@@ -2041,8 +2001,7 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
   }
   if (a->pair) {
     // the classification's declaration rows give each new entry's bytes
-    const PairGpu G{a->in, a->chunk_off, prow, a->maxd, a->pool, a->g_keys, a->g_vals, a->g_mask,
-                    a->g_filt, a->g_ftab, a->fmask, a->g_gfilt, a->gmask, a->nseg, a->status};
+    const PairGpu G = pair_gpu(a, prow);
     const int crc = xcg_pair_decode_commit(a->pair, &G, stream);
     (void)hipFreeAsync(pair_mem, stream);
     if (dfull) (void)hipFreeAsync(dfull, stream);
@@ -2050,19 +2009,19 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
     return hipGetLastError() == hipSuccess ? 0 : -5;
   }
   if (a->lru) {
-    hipLaunchKernelGGL(dec_replace_kernel, grid, block, 0, stream, p, (const uint4*)raw, (const uint4*)evs, a->pool);
+    hipLaunchKernelGGL(dec_replace_kernel, grid, block, 0, stream, p, (const uint4*)raw, (const uint4*)evs, a->g.pool);
     const int crc = xcg_lru_commit(&lb, a->lru, stream);
     (void)hipFreeAsync(lru_mem, stream);
     if (crc) return crc;
   } else {
     const uint64_t slots = (uint64_t)a->x_mask + 1;
-    const FiltSet fs{a->g_filt, a->g_ftab, a->fmask, a->g_gfilt, a->gmask};
+    const FiltSet fs = filters_of(a->g);
     if (nconf)
       hipLaunchKernelGGL(decode_commit_kernel<true>, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, stream, p,
-                         a->pool, a->nseg, a->seg_cap, fs);
+                         a->g.pool, a->g.nseg, a->g.seg_cap, fs);
     else
       hipLaunchKernelGGL(decode_commit_kernel<false>, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, stream, p,
-                         a->pool, a->nseg, a->seg_cap, fs);
+                         a->g.pool, a->g.nseg, a->g.seg_cap, fs);
     seg3.end();
   }
   if (occ_mem) (void)hipFreeAsync(occ_mem, stream);
@@ -2071,21 +2030,19 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
 }
 
 // One decode() call on an unbounded cache in one launch (decode_small_kernel).
-extern "C" int xcg_launch_decode_small(const uint8_t* in, uint32_t len, uint64_t* g_keys, uint64_t* g_vals,
-                                       uint32_t g_mask, uint8_t* pool, uint32_t* nseg, uint32_t seg_cap,
-                                       uint32_t* filt, uint32_t* ftab, uint32_t fmask, uint32_t* gfilt, uint32_t gmask,
-                                       int32_t* status, void* scratch, uint32_t ops_cap, uint8_t* out, uint64_t out_cap,
+extern "C" int xcg_launch_decode_small(const uint8_t* in, uint32_t len, const XcgCacheView* g, int32_t* status,
+                                       void* scratch, uint32_t ops_cap, uint8_t* out, uint64_t out_cap,
                                        uint64_t* win_hash, uint8_t* win_seg, uint64_t win_count, uint64_t* res,
                                        uint64_t* tim, uint32_t* flag, uint32_t seq, hipStream_t stream) {
   using namespace xcg;
   SmallDec a;
   a.in = in;
   a.len = len;
-  a.g = HashTab{g_keys, g_vals, g_mask};
-  a.pool = pool;
-  a.nseg = nseg;
-  a.seg_cap = seg_cap;
-  a.fs = FiltSet{filt, ftab, fmask, gfilt, gmask};
+  a.g = tab_of(*g);
+  a.pool = g->pool;
+  a.nseg = g->nseg;
+  a.seg_cap = g->seg_cap;
+  a.fs = filters_of(*g);
   a.status = status;
   a.ops = (uint4*)scratch;
   a.opv = (uint64_t*)(a.ops + ops_cap);

@@ -2886,18 +2886,18 @@ extern "C" int xcg_launch_encode_stream(const XcgStreamArgs* a, int* rounds_out,
   if (n == 0) return 0;
   EncParams prm{a->in, a->chunk_off, a->chunk_len, n, a->flags, a->out, a->out_off, a->out_len, a->stats, a->status};
   prm.max_len = (a->maxd - 1) * SEG + (SEG - 1);     // maxd = max_chunk_len / 2048 + 1
-  prm.g = HashTab{a->g_keys, a->g_vals, a->g_mask};
-  prm.pool = a->pool;
+  prm.g = tab_of(a->g);
+  prm.pool = a->g.pool;
   prm.b = HashTab{a->b_keys, a->b_vals, a->b_mask};
   prm.decl = (uint4*)a->decl;
   prm.ndecl = a->ndecl;
   prm.maxd = a->maxd;
   prm.changed = a->changed;
-  prm.nseg = a->nseg;
+  prm.nseg = a->g.nseg;
   prm.bcount = a->bcount;
   prm.lds_filter_keys = xcg_lds_filter_keys();
   if (prm.lds_filter_keys == LFK_AUTO)
-    prm.lds_filter_keys = 16ull * ((uint64_t)a->fmask + 1) > (2ull << 20) ? 0u : xcg::LDS_FILTER_KEYS_DEFAULT;
+    prm.lds_filter_keys = 16ull * ((uint64_t)a->g.fmask + 1) > (2ull << 20) ? 0u : xcg::LDS_FILTER_KEYS_DEFAULT;
   prm.lds_prefilter_keys = __atomic_load_n(&g_lds_prefilter_keys, __ATOMIC_RELAXED);
   prm.ptime = a->ptime;
   prm.ev = (uint4*)a->ev;
@@ -2905,8 +2905,8 @@ extern "C" int xcg_launch_encode_stream(const XcgStreamArgs* a, int* rounds_out,
   prm.maxe = a->maxe;
   prm.eo = a->ev ? a->eo : nullptr;
   prm.rs = RestartArgs{};
-  const size_t tbytes = ((size_t)a->fmask + 1) * 16;
-  const size_t gbytes = ((size_t)a->gmask + 1) * 4;
+  const size_t tbytes = ((size_t)a->g.fmask + 1) * 16;
+  const size_t gbytes = ((size_t)a->g.gmask + 1) * 4;
   FlagsEvent flags_ev(a->flags_ev);
   int dev = 0;
   int cus = 0;
@@ -3007,7 +3007,7 @@ extern "C" int xcg_launch_encode_stream(const XcgStreamArgs* a, int* rounds_out,
   // Round 0: every chunk against the persistent cache + its own declarations.
   prm.use_b = false;
   prm.skip_below = 0;
-  prm.lf = LaneFilter{a->g_filt, (const u32x4*)a->g_ftab, a->fmask, a->g_gfilt, a->gmask};
+  prm.lf = LaneFilter{a->g.filt, (const u32x4*)a->g.ftab, a->g.fmask, a->g.gfilt, a->g.gmask};
   HashTab tabs[2] = {HashTab{a->b_keys, a->b_vals, a->b_mask}, HashTab{a->b2_keys, a->b2_vals, a->b_mask}};
   const HashTab rt{a->r_keys, a->r_vals, a->r_mask};
   // (a) by probing the windows (a_bits null: the conservative flag)
@@ -3022,8 +3022,8 @@ extern "C" int xcg_launch_encode_stream(const XcgStreamArgs* a, int* rounds_out,
   static const bool pf_off = getenv("XCG_NO_PREFIX_FILTERS") != nullptr;   // (A/B runs: one slice)
   const uint32_t pfdiv = pf_off ? 0u : (n + PREFIX_FILTERS - 1) / PREFIX_FILTERS;   // chunks per slice of the round's LDS filter
   auto prep = [&](int t, bool verify, uint32_t what) -> bool {
-    RoundPrep rp{tabs[t], a->r_filt, a->g_filt, (u32x4*)a->r_ftab, (const u32x4*)a->g_ftab, (uint32_t)(tbytes / 16),
-                 a->r_gfilt, a->g_gfilt, (uint32_t)(gbytes / 4), a->nseg, a->bcount, a->changed,
+    RoundPrep rp{tabs[t], a->r_filt, a->g.filt, (u32x4*)a->r_ftab, (const u32x4*)a->g.ftab, (uint32_t)(tbytes / 16),
+                 a->r_gfilt, a->g.gfilt, (uint32_t)(gbytes / 4), a->g.nseg, a->bcount, a->changed,
                  verify ? rt : HashTab{nullptr, nullptr, 0u}, a->vflags, at, a->a_bits, n, a->need,
                  rs_rounds ? a->bad_t : nullptr, rs_rounds ? a->bad_hi : nullptr, what};
     hipLaunchKernelGGL(round_prep_kernel, dim3(4 * dev_cus), dim3(256), 0, stream, rp);
@@ -3047,7 +3047,7 @@ extern "C" int xcg_launch_encode_stream(const XcgStreamArgs* a, int* rounds_out,
     hipLaunchKernelGGL(seed_tiling_kernel, dim3((seed_waves + 3) / 4), dim3(256), 0, stream, a->in, a->chunk_off,
                        a->chunk_len, n, a->maxd, (uint4*)a->decl, a->ndecl, a->nhits, a->changed,
                        fuse ? tabs[cur] : HashTab{nullptr, nullptr, 0u},
-                       FiltSet{a->r_filt, a->r_ftab, a->fmask, a->r_gfilt, a->gmask}, a->bcount, a->status, pfdiv);
+                       FiltSet{a->r_filt, a->r_ftab, a->g.fmask, a->r_gfilt, a->g.gmask}, a->bcount, a->status, pfdiv);
     if (fuse) hipLaunchKernelGGL(filt_prefix_kernel, dim3(FILT_WORDS / 256), dim3(256), 0, stream, a->r_filt);
     seed_built = fuse;
   } else {
@@ -3074,18 +3074,17 @@ extern "C" int xcg_launch_encode_stream(const XcgStreamArgs* a, int* rounds_out,
     const uint32_t parts = (a->maxd + 255) / 256;
     uint32_t* seg_base = (uint32_t*)a->hits;       // (free once the rounds are over: n words)
     hipLaunchKernelGGL(commit_scan_kernel, dim3(1), dim3(1024), 0, stream, (const uint32_t*)a->ndecl, n, seg_base,
-                       a->nseg, gate);
+                       a->g.nseg, gate);
     hipLaunchKernelGGL(commit_kernel, dim3(n * parts), dim3(256), 0, stream, (const uint4*)a->decl,
-                       (const uint32_t*)a->ndecl, n, a->maxd, a->in, a->chunk_off, prm.g, a->pool,
-                       (const uint32_t*)seg_base, a->seg_cap,
-                       FiltSet{a->g_filt, a->g_ftab, a->fmask, a->g_gfilt, a->gmask}, a->status, gate);
+                       (const uint32_t*)a->ndecl, n, a->maxd, a->in, a->chunk_off, prm.g, a->g.pool,
+                       (const uint32_t*)seg_base, a->g.seg_cap, filters_of(a->g), a->status, gate);
   };
   auto build = [&](int t, bool verify, uint32_t what) -> bool {
     if (!prep(t, verify, what)) return false;
     const uint64_t nthreads = (uint64_t)n * a->maxd;
     hipLaunchKernelGGL(build_batch_table_kernel, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, stream,
                        (const uint4*)a->decl, (const uint32_t*)a->ndecl, n, a->maxd, tabs[t],
-                       FiltSet{a->r_filt, a->r_ftab, a->fmask, a->r_gfilt, a->gmask}, a->bcount, a->status, what,
+                       FiltSet{a->r_filt, a->r_ftab, a->g.fmask, a->r_gfilt, a->g.gmask}, a->bcount, a->status, what,
                        pfdiv);
     if (what & PREP_FILTERS)
       hipLaunchKernelGGL(filt_prefix_kernel, dim3(FILT_WORDS / 256), dim3(256), 0, stream, a->r_filt);
@@ -3121,7 +3120,7 @@ extern "C" int xcg_launch_encode_stream(const XcgStreamArgs* a, int* rounds_out,
     prm.use_b = true;
     prm.b = tabs[cur];
     prm.skip_below = seeded ? 0 : fc + 1;            // (seeded: round 1 parses every chunk)
-    prm.lf = LaneFilter{a->r_filt, (const u32x4*)a->r_ftab, a->fmask, a->r_gfilt, a->gmask, pfdiv};
+    prm.lf = LaneFilter{a->r_filt, (const u32x4*)a->r_ftab, a->g.fmask, a->r_gfilt, a->g.gmask, pfdiv};
     if (keep && a->need_given) prm.need = a->need;   // the rest stand under the kept lists
     const bool rs = keep && a->need_given && a->restart && a->bslot && prm.eo;
     if (rs) run_restarted();

@@ -6,6 +6,7 @@
 // wave prefix scans over per-lane 32-byte segment sums (segments [l, l+64) of
 // the 4 KiB span [p, p + 4096)), then the lane rolls exactly like
 // RollingHash::roll (xcodec_hash.h:57-70).
+#include "xcg_args.h"
 #include "xcg_device.h"
 
 namespace xcg {

@@ -559,9 +559,15 @@ xcg::ScanArgs scan_args(XcgLruState* L, uint32_t* nseg) {
 }
 
 LruBatch batch_of(const XcgStreamArgs& a) {
-  return LruBatch{a.n, a.in, a.chunk_off, a.decl, a.ndecl, a.maxd, a.ev, a.nev, a.maxe, 0, a.need,
-                  a.g_keys, a.g_vals, a.g_mask, a.pool, a.nseg, a.g_filt, a.g_ftab, a.fmask, a.g_gfilt, a.gmask,
-                  a.status, (uint64_t)a.n * a.maxe, a.bad_t, a.bad_hi};
+  LruBatch b{};
+  b.n = a.n; b.in = a.in; b.chunk_off = a.chunk_off;
+  b.decl = a.decl; b.ndecl = a.ndecl; b.maxd = a.maxd;
+  b.ev = a.ev; b.nev = a.nev; b.maxe = a.maxe;
+  b.need = a.need; b.bad_t = a.bad_t; b.bad_hi = a.bad_hi;
+  b.g = a.g;
+  b.status = a.status;
+  b.ev_bound = (uint64_t)a.n * a.maxe;
+  return b;
 }
 
 // Eviction times from a batch's references: tau, first hits, the LRU-order
@@ -574,7 +580,7 @@ int lru_times(const LruBatch& b, XcgLruState* L, bool check, hipStream_t st, boo
   using namespace xcg;
   const uint32_t n = b.n;
   hipLaunchKernelGGL(lru_prep_kernel, dim3(1), dim3(1024), 0, st, n, b.nev, b.ndecl, b.maxe, L->C,
-                     (const uint32_t*)b.nseg, L->ev_base, L->enter_base, b.need, L->tot, skip);
+                     (const uint32_t*)b.g.nseg, L->ev_base, L->enter_base, b.need, L->tot, skip);
   const unsigned cg = grid_for(L->C) < 1024 ? grid_for(L->C) : 1024;
   hipLaunchKernelGGL(lru_fill64x4_kernel, dim3(cg), dim3(256), 0, st, Fill64{L->hmin, L->C, NEVER},
                      Fill64{L->tau, L->C, NEVER}, Fill64{nullptr, 0u, 0ull}, Fill64{nullptr, 0u, 0ull}, skip);
@@ -615,7 +621,7 @@ int lru_seed_guess(const XcgStreamArgs& a, XcgLruState* L, hipStream_t st) {
   using namespace xcg;
   const uint32_t n = a.n;
   const unsigned cg = grid_for(L->C) < 1024 ? grid_for(L->C) : 1024;
-  const HashTab g{a.g_keys, a.g_vals, a.g_mask}, b{a.b_keys, a.b_vals, a.b_mask};   // (b: the rounds rebuild it)
+  const HashTab g = tab_of(a.g), b{a.b_keys, a.b_vals, a.b_mask};   // (b: the rounds rebuild it)
   (void)cg;
   hipLaunchKernelGGL(lru_fill64x4_kernel, dim3(1024), dim3(256), 0, st, Fill64{b.keys, b.mask + 1, EMPTY_KEY},
                      Fill64{b.vals, b.mask + 1, ~0ull}, Fill64{L->hmin, L->C, NEVER}, Fill64{L->tau, L->C, NEVER},
@@ -636,7 +642,7 @@ int lru_seed_guess(const XcgStreamArgs& a, XcgLruState* L, hipStream_t st) {
                        (const uint32_t*)a.ndecl, a.maxd, a.chunk_len, g, b, cnt, (const uint32_t*)L->enter_base,
                        (const uint32_t*)L->tot, L->C, L->hmin, L->tau, 0, pt);
     hipLaunchKernelGGL(lru_prep_kernel, dim3(1), dim3(1024), 0, st, n, (const uint32_t*)a.nev, (const uint32_t*)cnt,
-                       a.maxe, L->C, (const uint32_t*)a.nseg, L->ev_base, L->enter_base, a.need, L->tot,
+                       a.maxe, L->C, (const uint32_t*)a.g.nseg, L->ev_base, L->enter_base, a.need, L->tot,
                        (const uint32_t*)nullptr);
     hipLaunchKernelGGL(lru_seed_classify_kernel, wgrid, dim3(256), 0, st, n, (const uint4*)a.decl,
                        (const uint32_t*)a.ndecl, a.maxd, a.chunk_len, g, b, cnt, (const uint32_t*)L->enter_base,
@@ -667,21 +673,21 @@ int lru_commit_dev(const LruBatch* bp, XcgLruState* L, const uint32_t* gate, hip
   ScanArgs fa = scan_args(L, nullptr);
   fa.gate = gate;
   if (run_scan<SK_FREE>(L, fa, C, st)) return -5;
-  const HashTab g{b.g_keys, b.g_vals, b.g_mask};
-  const FiltSet fs{b.g_filt, b.g_ftab, b.fmask, b.g_gfilt, b.gmask};
-  Wipe w{g, b.g_filt, (u32x4*)b.g_ftab, b.fmask + 1, b.g_gfilt, b.gmask + 1};
+  const HashTab g = tab_of(b.g);
+  const FiltSet fs = filters_of(b.g);
+  Wipe w{g, fs.filt, (u32x4*)fs.ftab, fs.fmask + 1, fs.gfilt, fs.gmask + 1};
   hipLaunchKernelGGL(lru_wipe_kernel, dim3(1024), dim3(256), 0, st, w, gate);
   hipLaunchKernelGGL(lru_insert_alive_kernel, dim3(grid_for(C)), dim3(256), 0, st, C, (const uint32_t*)L->alive,
                      (const uint64_t*)L->skey, g, fs, b.status, gate);
   const uint64_t waves = (uint64_t)n * b.maxd;
   hipLaunchKernelGGL(lru_insert_new_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, n,
                      (const uint4*)b.decl, b.ndecl, b.maxd, (const uint32_t*)L->enter_base,
-                     (const uint32_t*)L->freel, b.in, b.chunk_off, L->skey, L->alive, g, b.pool, fs, b.status, gate);
+                     (const uint32_t*)L->freel, b.in, b.chunk_off, L->skey, L->alive, g, b.g.pool, fs, b.status, gate);
   const EvRows R{(const uint4*)b.ev, b.nev, (const uint32_t*)L->ev_base, b.maxe, b.dense != 0};
   hipLaunchKernelGGL(lru_lastref_kernel, dim3((n + 3) / 4), dim3(256), 0, st, n, R, (const uint32_t*)L->enter_base,
                      (const uint32_t*)L->freel, g, L->clock, L->lastref, L->evslot, L->evtime, gate);
   {
-    ScanArgs qa = scan_args(L, b.nseg);
+    ScanArgs qa = scan_args(L, b.g.nseg);
     qa.gate = gate;
     if (run_scan<SK_QUEUE>(L, qa, (uint64_t)C + b.ev_bound, st)) return -5;
   }

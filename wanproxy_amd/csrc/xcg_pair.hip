@@ -1590,14 +1590,14 @@ int ensure_front_arrays(XcgPairState* P) {
 
 // G from the state: wipe, then every primary slot and live own disk block.
 void pair_rebuild(XcgPairState* P, const PairGpu& G, hipStream_t st) {
-  const HashTab g{G.g_keys, G.g_vals, G.g_mask};
-  const FiltSet fs{G.g_filt, G.g_ftab, G.fmask, G.g_gfilt, G.gmask};
-  PairWipe wp{g, G.g_filt, (u32x4*)G.g_ftab, G.fmask + 1, G.g_gfilt, G.gmask + 1, G.nseg};
+  const HashTab g = tab_of(G.g);
+  const FiltSet fs = filters_of(G.g);
+  PairWipe wp{g, fs.filt, (u32x4*)fs.ftab, fs.fmask + 1, fs.gfilt, fs.gmask + 1, G.g.nseg};
   hipLaunchKernelGGL(pair_wipe_kernel, dim3(1024), dim3(256), 0, st, wp);
   XcgDiskState* K = P->disk;
   hipLaunchKernelGGL(pair_rebuild_kernel, dim3(grid_for((uint64_t)P->C + P->D)), dim3(256), 0, st,
                      (const uint64_t*)P->pkey, P->C, (const uint64_t*)K->dkey, (const uint64_t*)K->dent,
-                     (const uint32_t*)K->dxuid, P->D, P->nb, (uint32_t)P->xuid, K->dclock, g, fs, G.nseg, G.status);
+                     (const uint32_t*)K->dxuid, P->D, P->nb, (uint32_t)P->xuid, K->dclock, g, fs, G.g.nseg, G.status);
   P->gclock = K->dclock;
   P->gstale = false;
 }
@@ -1648,11 +1648,11 @@ int pair_commit(XcgPairState* P, const PairGpu& G, hipStream_t st) {
   P->stg_cap = sc;
   if (nmove) {
     hipLaunchKernelGGL(pair_stage_kernel, dim3((nmove + 3) / 4), dim3(256), 0, st, (const uint4*)P->moves,
-                       (const PairCnt*)P->cnt, (const uint8_t*)G.pool, P->staging);
+                       (const PairCnt*)P->cnt, (const uint8_t*)G.g.pool, P->staging);
     hipLaunchKernelGGL(pair_move_kernel, dim3((nmove + 4 * MOVES_PER_WAVE - 1) / (4 * MOVES_PER_WAVE)), dim3(256), 0, st,
                        (const uint4*)P->moves,
                        (const PairCnt*)P->cnt, G.in, G.chunk_off, (const uint4*)G.decl, G.maxd,
-                       (const uint8_t*)P->staging, G.pool);
+                       (const uint8_t*)P->staging, G.g.pool);
   }
   std::swap(P->lru, P->lru2);
   P->pcount = pc;
@@ -1683,8 +1683,12 @@ int pair_sync_front(XcgPairState* P, const PairGpu& G, hipStream_t st) {
 }
 
 PairGpu gpu_of(const XcgStreamArgs& a) {
-  return PairGpu{a.in, a.chunk_off, a.decl, a.maxd, a.pool, a.g_keys, a.g_vals, a.g_mask,
-                 a.g_filt, a.g_ftab, a.fmask, a.g_gfilt, a.gmask, a.nseg, a.status};
+  PairGpu G{};
+  G.in = a.in; G.chunk_off = a.chunk_off;
+  G.decl = a.decl; G.maxd = a.maxd;
+  G.g = a.g;
+  G.status = a.status;
+  return G;
 }
 
 // The disk's device arrays, on the first front's device.
@@ -2439,7 +2443,7 @@ int xcg_pair_decode_pass(XcgPairState* P, const PairGpu* G, const void* d_rows, 
                          const uint64_t* d_cnt, uint32_t n, uint64_t rows, uint32_t maxd, int* same, hipStream_t st) {
   RowSrc rs{1, n, maxd, (const uint4*)d_rows, nullptr, 0u, d_base, d_cnt, rows, nullptr, nullptr, nullptr};
   PassOut o;
-  const HashTab g{G->g_keys, G->g_vals, G->g_mask};
+  const HashTab g = tab_of(G->g);
   const int rc = replay(P, rs, g, true, &o, st);
   if (rc) return rc;
   if (o.split) return -95;
@@ -2473,7 +2477,7 @@ int xcg_pair_encode_stream(const XcgStreamArgs* a0, XcgPairState* P, int* rounds
   uint32_t i0 = 0;
   using clk = std::chrono::steady_clock;
   auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-  const HashTab g{a0->g_keys, a0->g_vals, a0->g_mask};
+  const HashTab g = tab_of(a0->g);
   while (i0 < n) {
     const clk::time_point t0 = clk::now();
     // what is left in equal parts of at most `per` chunks (no short tail

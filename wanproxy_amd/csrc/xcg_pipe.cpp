@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/xcgpu.h"
+#include "xcg_args.h"
 
 namespace {
 
@@ -123,10 +124,6 @@ uint64_t decoded_bound(const uint8_t* enc, uint64_t n) {
 }
 
 }  // namespace
-
-// (xcg_api.hip) registry contexts a connecting pipe holds while it lives
-extern "C" void xcg_registry_hold(xcg_ctx* c);
-extern "C" void xcg_registry_release(xcg_ctx* c);
 
 struct xcg_pipe {
   xcg_ctx* enc;
