@@ -26,6 +26,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <map>
+#include <set>
 #include <string>
 
 #include "../include/xcgpu.h"
@@ -119,8 +120,20 @@ inline xcg_window *window_for(const void *decoder, xcg_ctx *ctx)
 	return w;
 }
 
+/* The hashes an XCodecDecoder returned as unknown and has not looked at since:
+ * what XCodecPipePair <ASK>s for, so the only entries a <LEARN> may enter or
+ * replace in the host cache behind the engine's back
+ * (xcodec/xcodec_pipe_pair.cc:300-328).  Kept beside the object like the
+ * window; the decoder's next decode() carries them over to the engine. */
+inline std::map<const void *, std::set<uint64_t> >& asked_map()
+{
+	static std::map<const void *, std::set<uint64_t> > asked;
+	return asked;
+}
+
 inline void forget_window(const void *decoder)
 {
+	asked_map().erase(decoder);
 	std::map<const void *, xcg_window *>::iterator it = window_map().find(decoder);
 	if (it == window_map().end())
 		return;

@@ -15,6 +15,7 @@
  */
 #include <string.h>
 
+#include <map>
 #include <set>
 #include <vector>
 
@@ -295,6 +296,26 @@ XCodecDecoder::decode(Buffer *output, Buffer *input, std::set<uint64_t>& unknown
 	if (win == NULL)
 		HALT(log_) << "No device memory for the XCodec window.";
 
+	/*
+	 * What this decoder asked for and a <LEARN> has answered since is in the
+	 * host cache only -- entered, or, on name reuse, replaced under a hash the
+	 * engine may hold with the old bytes (another pipe of the same peer cache
+	 * learned it first, xcodec/xcodec_pipe_pair.cc:312-327).  The engine's
+	 * cache takes them now, in the order the <LEARN>s named them (<ASK>s go
+	 * out sorted), as its own lookup-then-replace-or-enter.
+	 */
+	std::map<const void *, std::set<uint64_t> >::iterator asked = xcgpu_binding::asked_map().find(this);
+	if (asked != xcgpu_binding::asked_map().end()) {
+		for (std::set<uint64_t>::const_iterator it = asked->second.begin(); it != asked->second.end(); ++it) {
+			BufferSegment *seg = cache_->lookup(*it);
+			if (seg == NULL)
+				continue;
+			xcg_cache_enter_host(ctx, *it, seg->data());
+			seg->unref();
+		}
+		xcgpu_binding::asked_map().erase(asked);
+	}
+
 	/* call scratch kept across calls (a std::vector zero-fills what it grows:
 	 * per call that was 512 KiB of unknown-hash room alone) */
 	static thread_local std::vector<uint8_t> in, out;
@@ -468,6 +489,7 @@ XCodecDecoder::decode(Buffer *output, Buffer *input, std::set<uint64_t>& unknown
 				continue;
 			}
 			unknown_hashes.insert(unk[k]);
+			xcgpu_binding::asked_map()[this].insert(unk[k]);
 		}
 		return (true);
 	}

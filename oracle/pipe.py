@@ -6,8 +6,9 @@ pieces of XCODEC_PIPE_MAX_FRAME / 2 = 512 KiB (:585-600), each one
 XCodecEncoder::encode() call on the codec's cache, framed as <FRAME> 0x02
 BE32(len) data (:620-628); an empty buffer emits <EOS> 0xFC (:632-636).  The
 frame payloads come from the oracle encoder (oracle.lib), itself pinned to the
-reference; the framing bytes are these few lines.  The reference pipe pair
-itself is not built here: its <HELLO> needs libuuid's header.
+reference; the framing bytes are these few lines.  They are pinned to the
+reference pipe pair itself (oracle/refpipe.py, oracle/_ref/libppref.so) by
+tests/test_pipe_reference.py::test_oracle_framing_equals_reference.
 """
 from __future__ import annotations
 

@@ -1,0 +1,114 @@
+"""The pipe-pair protocol layer (xcg_pipe_*, wanproxy_amd/csrc/xcg_pipe.cpp)
+against the reference's XCodecPipePair: the scripted conversations of
+tests/pipe_cases.py, run on the engine (E) and on the reference pipe pair over
+the integration/ adapters (D, oracle/_ref/libppdropin.so -- INTEGRATION.md §3b),
+must reproduce the transcripts the reference pipe pair over the reference codec
+produced (tests/golden/pipe.json), byte for byte; and a conversation with the
+engine on one end and the reference (R, oracle/_ref/libppref.so) on the other
+runs to the same transcript in both roles."""
+import json
+import os
+
+import pytest
+
+import pipe_cases as pc
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# The one case with two permitted outcomes (below): 65,537 distinct unknown
+# hashes in one decode, one more than the engine's unknown-hash set holds.
+OVER_CAPACITY = 'unknown_65537'
+
+
+@pytest.fixture(scope='module')
+def golden_pipe():
+    with open(os.path.join(ROOT, 'tests/golden/pipe.json')) as f:
+        return json.load(f)['conversations']
+
+
+@pytest.fixture(scope='module')
+def E():
+    from wanproxy_amd.xcgpu import connect_registry_clear
+    connect_registry_clear()
+    return pc.EngineImpl()
+
+
+@pytest.fixture(scope='module')
+def D():
+    from oracle import refpipe
+    if not refpipe.available('dropin'):
+        pytest.skip('oracle/_ref/libppdropin.so not built (needs the reference tree)')
+    return pc.RefImpl('dropin')
+
+
+@pytest.fixture(scope='module')
+def R():
+    from oracle import refpipe
+    if not refpipe.available('ref'):
+        pytest.skip('oracle/_ref/libppref.so not built (needs the reference tree)')
+    return pc.RefImpl('ref')
+
+
+def same(T, exp, name):
+    got = pc.record(T)
+    assert len(got) == len(exp)
+    for k, (g, e) in enumerate(zip(got, exp)):
+        assert g == e, f'{name}: step {k} ({pc.conversation(name).steps[k][:2]}) differs from the reference'
+
+
+@pytest.mark.parametrize('name', [n for n in pc.NAMES if n != OVER_CAPACITY])
+def test_engine_reproduces_reference(E, golden_pipe, name):
+    same(pc.run(pc.conversation(name), E), golden_pipe[name], name)
+
+
+def test_engine_over_unknown_capacity(E, golden_pipe):
+    """65,537 distinct unknown hashes in one decode.  The reference sends 129
+    <ASK> ops.  The engine's unknown-hash set holds 65,536 (UNKNOWN_CAP,
+    xcg_api.hip): it either matches the reference or fails loudly with
+    XCG_EOVERFLOW, nothing produced and nothing entered into the cache
+    (Known departures)."""
+    from wanproxy_amd.xcgpu import XCG_EOVERFLOW, XCGError
+    conv = pc.conversation(OVER_CAPACITY)
+    (uuid, limit), = conv.codecs.values()
+    codec = E.codec(uuid, limit)
+    pair = codec.pair()
+    try:
+        try:
+            o = pair.consume('dec', conv.steps[0].src)
+        except XCGError as e:
+            assert f'({XCG_EOVERFLOW})' in str(e)
+            pending, dcache = pair._state()
+            assert (pending, dcache) == (0, 0)
+        else:
+            same([o], golden_pipe[OVER_CAPACITY], OVER_CAPACITY)
+    finally:
+        pair.close()
+        codec.close()
+        E.reset()
+
+
+# D cannot express the over-capacity case: the decode adapter HALTs (aborts the
+# process) on an engine error, XCG_EOVERFLOW included.
+@pytest.mark.parametrize('name', [n for n in pc.NAMES if n != OVER_CAPACITY])
+def test_dropin_reproduces_reference(D, golden_pipe, name):
+    """The reference's xcodec_pipe_pair.cc, unchanged, over the GPU-backed
+    XCodecEncoder / XCodecDecoder adapters."""
+    same(pc.run(pc.conversation(name), D), golden_pipe[name], name)
+
+
+@pytest.mark.parametrize('engine_side', ['S', 'V'], ids=['engine_sends', 'engine_receives'])
+def test_engine_with_reference_peer(E, R, golden_pipe, engine_side):
+    """Conversations 4 and 6 joined (<ASK>/<LEARN> over merged frames, a reply
+    payload, <EOS> through <EOS_ACK> on both sides), the engine on one end and
+    the reference pipe pair on the other."""
+    conv = pc.conversation('ask_learn_eos')
+    T = pc.run(conv, {c: (E if c == engine_side else R) for c in conv.codecs})
+    got = pc.locals_of(conv, T)
+    for pipe, payload in conv.payloads.items():
+        assert got[pipe] == payload
+    for pipe in ('s1', 'r1'):
+        assert any(o.local_eos for st, o in zip(conv.steps, T) if o is not None and st.pipe == pipe)
+        assert any(o.peer_eos for st, o in zip(conv.steps, T) if o is not None and st.pipe == pipe)
+    same(T, golden_pipe['ask_learn_eos'], 'ask_learn_eos')

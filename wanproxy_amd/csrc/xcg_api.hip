@@ -696,7 +696,9 @@ int xcg_ctx_create_pair(int device, uint32_t flags, uint64_t memory_cache_limit_
 // the parent's connect: XCodecMemoryCache::connect (:340-346, an empty cache
 // of the same limit), XCodecCachePair::connect (:158-161: the primary's connect
 // over XCodecDisk::connect(uuid), xcodec_cache_disk.cc:640-690).
-int xcg_ctx_connect(xcg_ctx* parent, const char* uuid36, xcg_ctx** out) {
+// `hold`: the caller (a connecting pipe) takes its hold on the context before
+// g_reg_mu is released, so no registry clear can fall between the two.
+static int ctx_connect(xcg_ctx* parent, const char* uuid36, bool hold, xcg_ctx** out) {
   std::string key;
   if (!parent || !out || !uuid_key(uuid36, &key)) return XCG_EINVAL;
   *out = nullptr;
@@ -704,6 +706,7 @@ int xcg_ctx_connect(xcg_ctx* parent, const char* uuid36, xcg_ctx** out) {
   auto it = g_reg.find(key);
   if (it != g_reg.end()) {
     *out = it->second.ctx;
+    if (hold) ++g_holds[*out];
     return XCG_OK;
   }
   xcg_ctx* c = nullptr;
@@ -721,7 +724,12 @@ int xcg_ctx_connect(xcg_ctx* parent, const char* uuid36, xcg_ctx** out) {
   if (rc != XCG_OK) return rc;
   g_reg[key] = RegEntry{c, true};
   *out = c;
+  if (hold) ++g_holds[c];
   return XCG_OK;
+}
+
+int xcg_ctx_connect(xcg_ctx* parent, const char* uuid36, xcg_ctx** out) {
+  return ctx_connect(parent, uuid36, false, out);
 }
 
 // XCodecCache::enter(uuid, cache) (:113-117): a context the caller keeps.
@@ -757,9 +765,8 @@ void xcg_connect_registry_clear(void) {
 }
 
 // (xcg_pipe.cpp, not part of the ABI) a connecting pipe takes and drops its context
-extern "C" void xcg_registry_hold(xcg_ctx* c) {
-  std::lock_guard<std::mutex> lk(g_reg_mu);
-  ++g_holds[c];
+extern "C" int xcg_ctx_connect_hold(xcg_ctx* parent, const char* uuid36, xcg_ctx** out) {
+  return ctx_connect(parent, uuid36, true, out);
 }
 extern "C" void xcg_registry_release(xcg_ctx* c) {
   bool destroy = false;

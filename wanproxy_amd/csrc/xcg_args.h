@@ -295,5 +295,6 @@ extern "C" uint32_t xcg_decode_small_phases(void);
 extern "C" uint32_t xcg_decode_small_lds_in(void);
 
 // (xcg_api.hip for xcg_pipe.cpp) a connecting pipe takes and drops its registry context
-extern "C" void xcg_registry_hold(xcg_ctx* c);
+// (connect_hold: xcg_ctx_connect with the hold taken under the registry lock)
+extern "C" int xcg_ctx_connect_hold(xcg_ctx* parent, const char* uuid36, xcg_ctx** out);
 extern "C" void xcg_registry_release(xcg_ctx* c);

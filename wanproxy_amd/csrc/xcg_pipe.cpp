@@ -184,10 +184,13 @@ int xcg_pipe::decode_ops() {
         memcpy(u, b + 2, UUID_LEN);
         u[UUID_LEN] = 0;
         xcg_ctx* c = nullptr;
-        rc = xcg_ctx_connect(parent, u, &c);
-        if (rc == XCG_OK) rc = xcg_window_create(c, &win);
+        rc = xcg_ctx_connect_hold(parent, u, &c);                    // (held until xcg_pipe_destroy)
         if (rc != XCG_OK) break;
-        xcg_registry_hold(c);                                        // (until xcg_pipe_destroy)
+        rc = xcg_window_create(c, &win);
+        if (rc != XCG_OK) {
+          xcg_registry_release(c);
+          break;
+        }
         dec = c;
       }
       decoder = true;
