@@ -587,6 +587,13 @@ int xcg_debug_stream_kernel_time(double *ms, uint32_t *launches);
  * copy, 8 window, 9 commit, 10 results), microseconds.  Returns (and resets)
  * the call count. */
 uint32_t xcg_debug_decode_phases(double *us, uint32_t n);
+/* Diagnostics / tests: GPU memory the library holds now, in the whole process
+ * (every context, window, pair front, disk and zlib object, and the
+ * stream-ordered temporaries of calls in flight): out[0] device bytes, out[1]
+ * pinned host bytes, out[2] device allocations, out[3] pinned allocations.
+ * Back at its earlier values once everything made since is destroyed.  (A
+ * pair pool mapped with HIP virtual memory is not counted.) */
+void xcg_debug_mem_live(uint64_t out[4]);
 
 /* Every window hash: d_hash[s] = XCodecHash over d_x[s .. s+2048) for
  * s in [0, len - 2048]. */

@@ -24,15 +24,14 @@
 #include "../../include/xcgpu.h"
 #include "xcg_args.h"
 #include "xcg_cache.h"
+#include "xcg_devmem.h"
 
 // The persistent segment cache of a context: XCodecMemoryCache's
 // hash_map<Tag64, BufferSegment*> (xcodec/xcodec_cache.h:270) as an
 // open-addressed table in HBM plus a segment pool, and the two lane-probe
-// filters over it (see xcg_cache.h): the view the drivers get, and who owns
-// the pool.
-struct GpuCache : XcgCacheView {
-  bool pool_borrowed = false;   // (a pair front's pool: owned by its XcgPairState)
-};
+// filters over it (see xcg_cache.h): the view the drivers get.  (A pair
+// front's pool is its XcgPairState's: the context's owner never holds it.)
+using GpuCache = XcgCacheView;
 
 struct BatchScratch {
   uint32_t n_cap = 0, maxd = 0;
@@ -118,6 +117,7 @@ struct DecodeScratch {
 // of (hash, owned 2048-byte copy) and the number of declares made so far
 // (cursor = count mod 256).  One per XCodecDecoder; a context has a default.
 struct xcg_window {
+  xcg::DevMem mem;
   int device = 0;
   uint64_t* hash = nullptr;
   uint8_t* seg = nullptr;
@@ -164,6 +164,9 @@ struct xcg_ctx {
   uint8_t* zc_h = nullptr;
   size_t zc_cap = 0;
   uint32_t zc_seq = 0;
+  // Who frees what (xcg_devmem.h): the cache, the LRU arrays, the batch and decode scratch (each
+  // regrown as a whole), and the call blocks -- status words, staging, zero-copy block
+  xcg::DevMem mem_cache, mem_lru, mem_bs, mem_ds, mem_call;
 };
 
 namespace {
@@ -216,6 +219,7 @@ struct DeviceGuard {
 
 using xcg::FILT_WORDS;
 using xcg::PREFIX_FILTERS;
+using xcg::align_up;
 
 // A driver's return code (0 or a negative errno-like value) as an ABI status.
 int status_of(int rc) {
@@ -258,81 +262,55 @@ uint32_t pow2_at_least(uint64_t v) {
   return (uint32_t)p;
 }
 
-void free_cache(GpuCache& g) {
-  (void)hipFree(g.keys); (void)hipFree(g.vals); (void)hipFree(g.nseg);
-  if (!g.pool_borrowed) (void)hipFree(g.pool);
-  (void)hipFree(g.filt); (void)hipFree(g.ftab); (void)hipFree(g.gfilt);
-  g = GpuCache{};
+void free_cache(xcg_ctx* c) {
+  c->mem_cache.release_all();
+  c->g = GpuCache{};
 }
 
-void free_lru(XcgLruState& L) {
-  (void)hipFree(L.skey); (void)hipFree(L.lastref); (void)hipFree(L.queue); (void)hipFree(L.queue2);
-  (void)hipFree(L.ptime); (void)hipFree(L.hmin); (void)hipFree(L.wpop); (void)hipFree(L.tau);
-  (void)hipFree(L.alive); (void)hipFree(L.freel); (void)hipFree(L.part);
-  (void)hipFree(L.tot);
-  if (L.h_tot) (void)hipHostFree(L.h_tot);
+void free_lru(xcg_ctx* c) {
+  XcgLruState& L = c->lru;
+  c->mem_lru.release_all();
   if (L.tev) (void)hipEventDestroy((hipEvent_t)L.tev);
   const uint32_t C = L.C;
   L = XcgLruState{};
   L.C = C;
 }
 
-int alloc_lru(XcgLruState& L) {
+int alloc_lru(xcg_ctx* c) {
+  XcgLruState& L = c->lru;
+  xcg::DevMem& m = c->mem_lru;
+  L.mem = &m;
   const uint64_t C = L.C;
-  if (hipMalloc(&L.skey, 8 * C) != hipSuccess || hipMalloc(&L.lastref, 8 * C) != hipSuccess ||
-      hipMalloc(&L.queue, 4 * C) != hipSuccess || hipMalloc(&L.queue2, 4 * C) != hipSuccess ||
-      hipMalloc(&L.ptime, 8 * C) != hipSuccess || hipMalloc(&L.hmin, 8 * C) != hipSuccess ||
-      hipMalloc(&L.wpop, 8 * C) != hipSuccess || hipMalloc(&L.tau, 8 * C) != hipSuccess ||
-      hipMalloc(&L.alive, 4 * C) != hipSuccess || hipMalloc(&L.freel, 4 * C) != hipSuccess ||
-      hipMalloc(&L.tot, 64) != hipSuccess || hipHostMalloc(&L.h_tot, 64) != hipSuccess ||
+  if (!(m.dev(&L.skey, 8 * C) && m.dev(&L.lastref, 8 * C) && m.dev(&L.queue, 4 * C) && m.dev(&L.queue2, 4 * C) &&
+        m.dev(&L.ptime, 8 * C) && m.dev(&L.hmin, 8 * C) && m.dev(&L.wpop, 8 * C) && m.dev(&L.tau, 8 * C) &&
+        m.dev(&L.alive, 4 * C) && m.dev(&L.freel, 4 * C) && m.dev(&L.tot, 64) && m.pinned(&L.h_tot, 64)) ||
       hipMemset(L.lastref, 0, 8 * C) != hipSuccess) {
-    free_lru(L);
+    free_lru(c);
     return XCG_ENOMEM;
   }
   L.clock = 1;
   return XCG_OK;
 }
 
-void free_scratch(BatchScratch& b) {
-  (void)hipFree(b.b_keys); (void)hipFree(b.b_vals); (void)hipFree(b.r_filt); (void)hipFree(b.r_ftab);
-  (void)hipFree(b.decl); (void)hipFree(b.ndecl); (void)hipFree(b.changed); (void)hipFree(b.r_gfilt);
-  (void)hipFree(b.bcount);
-  (void)hipFree(b.b2_keys); (void)hipFree(b.b2_vals); (void)hipFree(b.r_keys); (void)hipFree(b.r_vals);
-  (void)hipFree(b.hits); (void)hipFree(b.nhits); (void)hipFree(b.need); (void)hipFree(b.vflags);
-  if (b.h_vflags) (void)hipHostFree(b.h_vflags);
-  if (b.h_changed) (void)hipHostFree(b.h_changed);
-  (void)hipFree(b.ev); (void)hipFree(b.nev); (void)hipFree(b.ev_base); (void)hipFree(b.enter_base);
-  (void)hipFree(b.ev_slot); (void)hipFree(b.ev_time);
-  (void)hipFree(b.eo); (void)hipFree(b.bad_t); (void)hipFree(b.bad_hi); (void)hipFree(b.bslot);
-  (void)hipFree(b.b_count); (void)hipFree(b.b_ev); (void)hipFree(b.b_eo); (void)hipFree(b.b_hits);
-  (void)hipFree(b.b_cnt); (void)hipFree(b.b_out); (void)hipFree(b.splice);
-  (void)hipFree(b.a_keys); (void)hipFree(b.a_vals); (void)hipFree(b.a_bits);
-  (void)hipFree(b.s_fold); (void)hipFree(b.s_work); (void)hipFree(b.s_info); (void)hipFree(b.s_rows);
-  (void)hipFree(b.s_qcnt); (void)hipFree(b.s_qkeys);
-  b = BatchScratch{};
+void free_scratch(xcg_ctx* c) {
+  c->mem_bs.release_all();
+  c->bs = BatchScratch{};
 }
-
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // The context's host-call staging: pinned host and device blocks of at least
 // the given sizes, and its own stream.
 int ensure_stage(xcg_ctx* c, size_t dbytes, size_t hbytes) {
   if (!c->call_st && hipStreamCreateWithFlags(&c->call_st, hipStreamNonBlocking) != hipSuccess) return XCG_EHIP;
+  // (a block that is replaced may still be in use by the last call's copies)
   if (dbytes > c->stage_d_cap) {
-    if (c->stage_d) { (void)hipStreamSynchronize(c->call_st); (void)hipFree(c->stage_d); }
-    c->stage_d = nullptr;
-    c->stage_d_cap = 0;
+    if (c->stage_d) (void)hipStreamSynchronize(c->call_st);
     const size_t want = dbytes < (1u << 20) ? (1u << 20) : dbytes;
-    if (hipMalloc(&c->stage_d, want) != hipSuccess) return XCG_ENOMEM;
-    c->stage_d_cap = want;
+    if (!c->mem_call.grow(&c->stage_d, &c->stage_d_cap, dbytes, want, want, xcg::MEM_DEV)) return XCG_ENOMEM;
   }
   if (hbytes > c->stage_h_cap) {
-    if (c->stage_h) { (void)hipStreamSynchronize(c->call_st); (void)hipHostFree(c->stage_h); }
-    c->stage_h = nullptr;
-    c->stage_h_cap = 0;
+    if (c->stage_h) (void)hipStreamSynchronize(c->call_st);
     const size_t want = hbytes < (1u << 20) ? (1u << 20) : hbytes;
-    if (hipHostMalloc(&c->stage_h, want, hipHostMallocDefault) != hipSuccess) return XCG_ENOMEM;
-    c->stage_h_cap = want;
+    if (!c->mem_call.grow(&c->stage_h, &c->stage_h_cap, hbytes, want, want, xcg::MEM_PINNED)) return XCG_ENOMEM;
   }
   return XCG_OK;
 }
@@ -383,18 +361,17 @@ int ensure_cache(xcg_ctx* c) {
   g.gmask = gw - 1;
   // A pair front's pool is its primary followed by the disk's blocks, mapped
   // by the pair state (one physical disk behind every front, xcg_pair.hip).
-  g.pool_borrowed = c->pair != nullptr;
+  xcg::DevMem& m = c->mem_cache;
   if (c->pair) g.pool = xcg_pair_state_pool(c->pair);
-  if (hipMalloc(&g.keys, 8ull * cap) != hipSuccess || hipMalloc(&g.vals, 8ull * cap) != hipSuccess ||
-      (!c->pair && hipMalloc(&g.pool, segs * (uint64_t)XCG_SEGMENT_LENGTH + 16) != hipSuccess) ||
-      hipMalloc(&g.nseg, 16) != hipSuccess || hipMalloc(&g.filt, 4ull * FILT_WORDS) != hipSuccess ||
-      hipMalloc(&g.ftab, 16ull * fb) != hipSuccess || hipMalloc(&g.gfilt, 4ull * gw) != hipSuccess) {
-    free_cache(g);
+  if (!(m.dev(&g.keys, 8ull * cap) && m.dev(&g.vals, 8ull * cap) &&
+        (c->pair || m.dev(&g.pool, segs * (uint64_t)XCG_SEGMENT_LENGTH + 16)) && m.dev(&g.nseg, 16) &&
+        m.dev(&g.filt, 4ull * FILT_WORDS) && m.dev(&g.ftab, 16ull * fb) && m.dev(&g.gfilt, 4ull * gw))) {
+    free_cache(c);
     return XCG_ENOMEM;
   }
   int rc = clear_cache(g);
-  if (rc == XCG_OK && c->bounded) rc = alloc_lru(c->lru);
-  if (rc) free_cache(g);
+  if (rc == XCG_OK && c->bounded) rc = alloc_lru(c);
+  if (rc) free_cache(c);
   return rc;
 }
 
@@ -402,10 +379,13 @@ int ensure_cache(xcg_ctx* c) {
 // per chunk of the scratch's capacity (SCREEN_QCAP keys; ~ the input's size
 // for 4 KiB packets), allocated by the first such call on the context --
 // whatever size of chunks grew the scratch before it -- and kept with it.
-int ensure_screen_queues(BatchScratch& b, uint32_t maxd) {
+int ensure_screen_queues(xcg_ctx* c, uint32_t maxd) {
+  BatchScratch& b = c->bs;
+  xcg::DevMem& m = c->mem_bs;
   if (maxd > 4 || (b.s_qcnt && b.s_qkeys)) return XCG_OK;
-  if (hipMalloc(&b.s_qcnt, 4ull * b.n_cap) != hipSuccess || hipMalloc(&b.s_qkeys, 4096ull * b.n_cap) != hipSuccess) {
-    (void)hipFree(b.s_qcnt); (void)hipFree(b.s_qkeys);
+  if (!(m.dev(&b.s_qcnt, 4ull * b.n_cap) && m.dev(&b.s_qkeys, 4096ull * b.n_cap))) {
+    m.release(b.s_qcnt);
+    m.release(b.s_qkeys);
     b.s_qcnt = nullptr; b.s_qkeys = nullptr;      // (the screen stays off; the parse decides alone)
   }
   return XCG_OK;
@@ -413,90 +393,68 @@ int ensure_screen_queues(BatchScratch& b, uint32_t maxd) {
 
 int ensure_scratch(xcg_ctx* c, uint32_t n, uint32_t maxd) {
   BatchScratch& b = c->bs;
-  if (b.decl && n <= b.n_cap && maxd <= b.maxd) return ensure_screen_queues(b, maxd);
-  free_scratch(b);
+  xcg::DevMem& m = c->mem_bs;
+  if (b.decl && n <= b.n_cap && maxd <= b.maxd) return ensure_screen_queues(c, maxd);
+  free_scratch(c);
   b.n_cap = n;
   b.maxd = maxd;
   const uint32_t cap = pow2_at_least(2ull * n * maxd + 1024);
   b.b_mask = cap - 1;
   b.r_mask = 2 * cap - 1;          // union of two rounds' hashes
   b.maxh = maxd + 8;
-  if (hipMalloc(&b.b_keys, 8ull * cap) != hipSuccess || hipMalloc(&b.b_vals, 8ull * cap) != hipSuccess ||
-      hipMalloc(&b.r_filt, 4ull * FILT_WORDS * PREFIX_FILTERS) != hipSuccess ||
-      hipMalloc(&b.r_ftab, 16ull * (c->g.fmask + 1)) != hipSuccess ||
-      hipMalloc(&b.decl, 16ull * n * maxd) != hipSuccess || hipMalloc(&b.ndecl, 4ull * n) != hipSuccess ||
-      hipMalloc(&b.changed, 16) != hipSuccess || hipHostMalloc(&b.h_changed, 16) != hipSuccess ||
-      hipMalloc(&b.r_gfilt, 4ull * (c->g.gmask + 1)) != hipSuccess || hipMalloc(&b.bcount, 4 * 64) != hipSuccess ||
-      hipMalloc(&b.b2_keys, 8ull * cap) != hipSuccess || hipMalloc(&b.b2_vals, 8ull * cap) != hipSuccess ||
-      hipMalloc(&b.r_keys, 16ull * cap) != hipSuccess || hipMalloc(&b.r_vals, 16ull * cap) != hipSuccess ||
-      hipMalloc(&b.hits, 8ull * n * (maxd + 8)) != hipSuccess || hipMalloc(&b.nhits, 4ull * n) != hipSuccess ||
-      hipMalloc(&b.need, 4ull * n) != hipSuccess || hipMalloc(&b.vflags, 16) != hipSuccess ||
-      hipHostMalloc(&b.h_vflags, 16) != hipSuccess || hipMalloc(&b.a_keys, 8ull * XCG_VERIFY_A_CAP) != hipSuccess ||
-      hipMalloc(&b.a_vals, 8ull * XCG_VERIFY_A_CAP) != hipSuccess ||
-      hipMalloc(&b.a_bits, 4ull * XCG_VERIFY_A_WORDS) != hipSuccess ||
-      hipMalloc(&b.s_fold, 4ull * 32768) != hipSuccess || hipMalloc(&b.s_work, 4ull * (n + 1)) != hipSuccess ||
-      hipMalloc(&b.s_info, 4ull * n) != hipSuccess || hipMalloc(&b.s_rows, 64ull * n) != hipSuccess) {
-    free_scratch(b);
+  if (!(m.dev(&b.b_keys, 8ull * cap) && m.dev(&b.b_vals, 8ull * cap) &&
+        m.dev(&b.r_filt, 4ull * FILT_WORDS * PREFIX_FILTERS) && m.dev(&b.r_ftab, 16ull * (c->g.fmask + 1)) &&
+        m.dev(&b.decl, 16ull * n * maxd) && m.dev(&b.ndecl, 4ull * n) && m.dev(&b.changed, 16) &&
+        m.pinned(&b.h_changed, 16) && m.dev(&b.r_gfilt, 4ull * (c->g.gmask + 1)) && m.dev(&b.bcount, 4 * 64) &&
+        m.dev(&b.b2_keys, 8ull * cap) && m.dev(&b.b2_vals, 8ull * cap) && m.dev(&b.r_keys, 16ull * cap) &&
+        m.dev(&b.r_vals, 16ull * cap) && m.dev(&b.hits, 8ull * n * (maxd + 8)) && m.dev(&b.nhits, 4ull * n) &&
+        m.dev(&b.need, 4ull * n) && m.dev(&b.vflags, 16) && m.pinned(&b.h_vflags, 16) &&
+        m.dev(&b.a_keys, 8ull * XCG_VERIFY_A_CAP) && m.dev(&b.a_vals, 8ull * XCG_VERIFY_A_CAP) &&
+        m.dev(&b.a_bits, 4ull * XCG_VERIFY_A_WORDS) && m.dev(&b.s_fold, 4ull * 32768) &&
+        m.dev(&b.s_work, 4ull * (n + 1)) && m.dev(&b.s_info, 4ull * n) && m.dev(&b.s_rows, 64ull * n))) {
+    free_scratch(c);
     return XCG_ENOMEM;
   }
-  ensure_screen_queues(b, maxd);
+  ensure_screen_queues(c, maxd);
   if (c->bounded || c->pair) {
     b.maxe = 2 * maxd + 64;        // declarations + REFs + collision lookups of one chunk
-    if (hipMalloc(&b.ev, 16ull * n * b.maxe) != hipSuccess || hipMalloc(&b.nev, 4ull * n) != hipSuccess ||
-        hipMalloc(&b.ev_base, 4ull * (n + 1)) != hipSuccess || hipMalloc(&b.enter_base, 4ull * (n + 1)) != hipSuccess ||
-        hipMalloc(&b.ev_slot, 4ull * n * b.maxe) != hipSuccess || hipMalloc(&b.ev_time, 8ull * n * b.maxe) != hipSuccess) {
-      free_scratch(b);
-      return XCG_ENOMEM;
-    }
     // restart backups for up to b_slots flagged chunks per pass (more re-parse from the start)
     b.b_slots = n < 256 ? n : 256;
     b.b_stride = (2ull * maxd * XCG_SEGMENT_LENGTH + 16 + 255) & ~255ull;   // >= xcg_encode_bound(max chunk)
-    if (hipMalloc(&b.eo, 4ull * n * b.maxe) != hipSuccess || hipMalloc(&b.bad_t, 4ull * n) != hipSuccess ||
-        hipMalloc(&b.bad_hi, 4ull * n) != hipSuccess || hipMalloc(&b.bslot, 4ull * n) != hipSuccess ||
-        hipMalloc(&b.b_count, 16) != hipSuccess || hipMalloc(&b.b_ev, 16ull * b.b_slots * b.maxe) != hipSuccess ||
-        hipMalloc(&b.b_eo, 4ull * b.b_slots * b.maxe) != hipSuccess ||
-        hipMalloc(&b.b_hits, 8ull * b.b_slots * b.maxh) != hipSuccess ||
-        hipMalloc(&b.b_cnt, 16ull * b.b_slots) != hipSuccess ||
-        hipMalloc(&b.b_out, b.b_stride * b.b_slots) != hipSuccess || hipMalloc(&b.splice, 16ull * n) != hipSuccess ||
+    if (!(m.dev(&b.ev, 16ull * n * b.maxe) && m.dev(&b.nev, 4ull * n) && m.dev(&b.ev_base, 4ull * (n + 1)) &&
+          m.dev(&b.enter_base, 4ull * (n + 1)) && m.dev(&b.ev_slot, 4ull * n * b.maxe) &&
+          m.dev(&b.ev_time, 8ull * n * b.maxe) && m.dev(&b.eo, 4ull * n * b.maxe) && m.dev(&b.bad_t, 4ull * n) &&
+          m.dev(&b.bad_hi, 4ull * n) && m.dev(&b.bslot, 4ull * n) && m.dev(&b.b_count, 16) &&
+          m.dev(&b.b_ev, 16ull * b.b_slots * b.maxe) && m.dev(&b.b_eo, 4ull * b.b_slots * b.maxe) &&
+          m.dev(&b.b_hits, 8ull * b.b_slots * b.maxh) && m.dev(&b.b_cnt, 16ull * b.b_slots) &&
+          m.dev(&b.b_out, b.b_stride * b.b_slots) && m.dev(&b.splice, 16ull * n)) ||
         hipMemset(b.splice, 0, 16ull * n) != hipSuccess || hipMemset(b.bad_t, 0xFF, 4ull * n) != hipSuccess ||
         hipMemset(b.bad_hi, 0, 4ull * n) != hipSuccess || hipMemset(b.b_count, 0, 16) != hipSuccess) {
-      free_scratch(b);
+      free_scratch(c);
       return XCG_ENOMEM;
     }
   }
   return XCG_OK;
 }
 
-void free_dscratch(DecodeScratch& d) {
-  (void)hipFree(d.x_keys); (void)hipFree(d.x_vals); (void)hipFree(d.x_latest); (void)hipFree(d.unknown);
-  (void)hipFree(d.u_keys);
-  (void)hipFree(d.x_owner); (void)hipFree(d.x_flag); (void)hipFree(d.dup_slot); (void)hipFree(d.dup_pos);
-  (void)hipFree(d.unknown_pos); (void)hipFree(d.nunknown); (void)hipFree(d.scratch);
-  (void)hipFree(d.chunk_tmp); (void)hipFree(d.d_tail);
-  if (d.h_scratch) (void)hipHostFree(d.h_scratch);
-  d = DecodeScratch{};
+void free_dscratch(xcg_ctx* c) {
+  c->mem_ds.release_all();
+  c->ds = DecodeScratch{};
 }
 
 int ensure_dchunks(xcg_ctx* c, uint32_t n) {
   DecodeScratch& d = c->ds;
-  if (!d.d_tail && hipMalloc(&d.d_tail, 16ull * 256) != hipSuccess) return XCG_ENOMEM;
-  if (d.chunk_tmp && n <= d.chunk_cap) return XCG_OK;
-  (void)hipFree(d.chunk_tmp);
-  d.chunk_tmp = nullptr;
-  d.chunk_cap = n < 1024 ? 1024 : n;
-  if (hipMalloc(&d.chunk_tmp, 32ull * d.chunk_cap) != hipSuccess) {
-    d.chunk_cap = 0;
-    return XCG_ENOMEM;
-  }
-  return XCG_OK;
+  if (!d.d_tail && !c->mem_ds.dev(&d.d_tail, 16ull * 256)) return XCG_ENOMEM;
+  const uint32_t cap = n < 1024 ? 1024 : n;
+  return c->mem_ds.grow(&d.chunk_tmp, &d.chunk_cap, cap, cap, 32ull * cap, xcg::MEM_DEV) ? XCG_OK : XCG_ENOMEM;
 }
 
 int window_alloc(int device, xcg_window** out) {
   xcg_window* w = new xcg_window;
   w->device = device;
-  if (hipMalloc(&w->hash, 8ull * 256) != hipSuccess || hipMalloc(&w->seg, 256ull * 2048) != hipSuccess ||
+  if (!(w->mem.dev(&w->hash, 8ull * 256) && w->mem.dev(&w->seg, 256ull * 2048)) ||
       hipMemset(w->hash, 0, 8ull * 256) != hipSuccess) {
-    (void)hipFree(w->hash); (void)hipFree(w->seg);
+    w->mem.release_all();
     delete w;
     return XCG_ENOMEM;
   }
@@ -506,7 +464,7 @@ int window_alloc(int device, xcg_window** out) {
 
 void window_free(xcg_window* w) {
   if (!w) return;
-  (void)hipFree(w->hash); (void)hipFree(w->seg);
+  w->mem.release_all();
   delete w;
 }
 
@@ -514,16 +472,16 @@ int ensure_dscratch(xcg_ctx* c, uint64_t max_extracts) {
   DecodeScratch& d = c->ds;
   const uint32_t cap = pow2_at_least(2 * max_extracts + 1024);
   if (d.x_keys && cap <= d.x_cap) return XCG_OK;
-  free_dscratch(d);
+  free_dscratch(c);
   d.x_cap = cap;
-  if (hipMalloc(&d.x_keys, 8ull * cap) != hipSuccess || hipMalloc(&d.x_vals, 8ull * cap) != hipSuccess ||
-      hipMalloc(&d.x_latest, 8ull * cap) != hipSuccess || hipMalloc(&d.unknown, 8ull * UNKNOWN_CAP) != hipSuccess ||
-      hipMalloc(&d.u_keys, 16ull * UNKNOWN_CAP) != hipSuccess ||
-      hipMalloc(&d.x_owner, 8ull * cap) != hipSuccess || hipMalloc(&d.x_flag, 4ull * cap) != hipSuccess ||
-      hipMalloc(&d.dup_slot, 4ull * (cap / 2)) != hipSuccess || hipMalloc(&d.dup_pos, 8ull * (cap / 2)) != hipSuccess ||
-      hipMalloc(&d.unknown_pos, 8ull * UNKNOWN_CAP) != hipSuccess || hipMalloc(&d.nunknown, 16) != hipSuccess ||
-      hipMalloc(&d.scratch, 64) != hipSuccess || hipHostMalloc(&d.h_scratch, 128) != hipSuccess) {
-    free_dscratch(d);
+  xcg::DevMem& m = c->mem_ds;
+  if (!(m.dev(&d.x_keys, 8ull * cap) && m.dev(&d.x_vals, 8ull * cap) && m.dev(&d.x_latest, 8ull * cap) &&
+        m.dev(&d.unknown, 8ull * UNKNOWN_CAP) && m.dev(&d.u_keys, 16ull * UNKNOWN_CAP) &&
+        m.dev(&d.x_owner, 8ull * cap) && m.dev(&d.x_flag, 4ull * cap) &&
+        m.dev(&d.dup_slot, 4ull * (cap / 2)) && m.dev(&d.dup_pos, 8ull * (cap / 2)) &&
+        m.dev(&d.unknown_pos, 8ull * UNKNOWN_CAP) && m.dev(&d.nunknown, 16) &&
+        m.dev(&d.scratch, 64) && m.pinned(&d.h_scratch, 128))) {
+    free_dscratch(c);
     return XCG_ENOMEM;
   }
   return XCG_OK;
@@ -796,19 +754,17 @@ int xcg_ctx_create_ex(int device, uint32_t flags, uint64_t cache_segments, xcg_c
   if (flags & ~(XCG_FLAG_OOB | XCG_FLAG_NULLCACHE)) return XCG_EINVAL;
   DeviceGuard g(device);
   xcg_ctx* c = new xcg_ctx{device, flags, nullptr, cache_segments, GpuCache{}, BatchScratch{}, 0, DecodeScratch{}};
-  if (hipMalloc(&c->d_status, 16) != hipSuccess || hipHostMalloc(&c->h_status, 16) != hipSuccess) {
-    (void)hipFree(c->d_status);
-    delete c;
-    return XCG_ENOMEM;
-  }
-  if (hipMemset(c->d_status, 0, 16) != hipSuccess ||
-      hipEventCreateWithFlags(&c->done_ev, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->flags_ev, hipEventDisableTiming) != hipSuccess) {
-    (void)hipFree(c->d_status);
+  auto fail = [&](int rc) {
+    c->mem_call.release_all();
     if (c->done_ev) (void)hipEventDestroy(c->done_ev);
     delete c;
-    return XCG_EHIP;
-  }
+    return rc;
+  };
+  if (!(c->mem_call.dev(&c->d_status, 16) && c->mem_call.pinned(&c->h_status, 16))) return fail(XCG_ENOMEM);
+  if (hipMemset(c->d_status, 0, 16) != hipSuccess ||
+      hipEventCreateWithFlags(&c->done_ev, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&c->flags_ev, hipEventDisableTiming) != hipSuccess)
+    return fail(XCG_EHIP);
   *out = c;
   return XCG_OK;
 }
@@ -817,19 +773,17 @@ void xcg_ctx_destroy(xcg_ctx* c) {
   if (!c) return;
   registry_forget(c);
   DeviceGuard g(c->device);
-  (void)hipFree(c->d_status);
-  if (c->h_status) (void)hipHostFree(c->h_status);
-  free_cache(c->g);
-  free_lru(c->lru);
-  free_scratch(c->bs);
-  free_dscratch(c->ds);
+  c->mem_call.release(c->d_status);
+  c->mem_call.release(c->h_status);
+  free_cache(c);
+  free_lru(c);
+  free_scratch(c);
+  free_dscratch(c);
   window_free(c->own_win);
   if (c->done_ev) (void)hipEventDestroy(c->done_ev);
   if (c->flags_ev) (void)hipEventDestroy(c->flags_ev);
   xcg_pair_state_destroy(c->pair);
-  if (c->stage_h) (void)hipHostFree(c->stage_h);
-  if (c->zc_h) (void)hipHostFree(c->zc_h);
-  (void)hipFree(c->stage_d);
+  c->mem_call.release_all();         // (the staging and the zero-copy block)
   if (c->call_st) (void)hipStreamDestroy(c->call_st);
   delete c;
 }
@@ -863,6 +817,10 @@ int xcg_cache_clear(xcg_ctx* c) {
 
 int xcg_last_rounds(xcg_ctx* c) { return c ? c->last_rounds : -1; }
 
+void xcg_debug_mem_live(uint64_t out[4]) {
+  for (int i = 0; i < 4; ++i) out[i] = xcg::HipMem::live[i].load();
+}
+
 int xcg_ctx_flags(const xcg_ctx* c, uint32_t* flags) {
   if (!c || !flags) return XCG_EINVAL;
   *flags = c->flags;
@@ -875,12 +833,10 @@ int host_seg_call(xcg_ctx* c, uint64_t hash, const uint8_t* in_seg, uint8_t* out
   DeviceGuard g(c->device);
   int rc = ensure_cache(c);
   if (rc != XCG_OK) return rc;
+  xcg::DevMem mem;                   // (freed when the call returns)
   uint8_t* d_seg = nullptr;
   int32_t* d_res = nullptr;
-  if (hipMalloc(&d_seg, XCG_SEGMENT_LENGTH) != hipSuccess || hipMalloc(&d_res, 4) != hipSuccess) {
-    (void)hipFree(d_seg);
-    return XCG_ENOMEM;
-  }
+  if (!(mem.dev(&d_seg, XCG_SEGMENT_LENGTH) && mem.dev(&d_res, 4))) return XCG_ENOMEM;
   rc = XCG_OK;
   if (mode == 0) {   // lookup
     if (xcg_launch_cache_lookup(&c->g, hash, d_seg, d_res, nullptr) != 0 ||
@@ -893,8 +849,6 @@ int host_seg_call(xcg_ctx* c, uint64_t hash, const uint8_t* in_seg, uint8_t* out
         hipMemcpy(res, d_res, 4, hipMemcpyDeviceToHost) != hipSuccess)
       rc = XCG_EHIP;
   }
-  (void)hipFree(d_seg);
-  (void)hipFree(d_res);
   return rc;
 }
 }  // namespace
@@ -910,8 +864,9 @@ int lru_host_call(xcg_ctx* c, uint64_t hash, const uint8_t* in_seg, uint8_t* out
   int rc = ensure_cache(c);
   if (rc != XCG_OK) return rc;
   // device scratch: [0, 2048) new bytes, [2048, 4096) old bytes, then the batch
+  xcg::DevMem mem;                   // (freed when the call returns)
   uint8_t* m = nullptr;
-  if (hipMalloc(&m, 8192) != hipSuccess) return XCG_ENOMEM;
+  if (!mem.dev(&m, 8192)) return XCG_ENOMEM;
   uint8_t* d_new = m;
   uint8_t* d_old = m + 2048;
   int32_t* d_res = (int32_t*)(m + 4096);
@@ -962,11 +917,11 @@ int lru_host_call(xcg_ctx* c, uint64_t hash, const uint8_t* in_seg, uint8_t* out
     }
     auto at = [&](const void* field) { return d_h + ((const uint8_t*)field - (const uint8_t*)&h); };
     XcgLruState& L = c->lru;
-    L.ev_base = (uint32_t*)at(h.ev_base);
-    L.enter_base = (uint32_t*)at(h.enter_base);
-    L.evslot = (uint32_t*)at(h.evslot);
-    L.evtime = (uint64_t*)at(h.evtime);
     LruBatch b{};
+    b.ev_base = (uint32_t*)at(h.ev_base);
+    b.enter_base = (uint32_t*)at(h.enter_base);
+    b.evslot = (uint32_t*)at(h.evslot);
+    b.evtime = (uint64_t*)at(h.evtime);
     b.n = 1; b.in = d_new; b.chunk_off = (const uint64_t*)at(&h.chunk_off);
     b.decl = at(h.decl); b.ndecl = (const uint32_t*)at(&h.ndecl); b.maxd = 1;
     b.ev = at(h.ev); b.nev = (const uint32_t*)at(&h.nev); b.maxe = 1;
@@ -978,23 +933,11 @@ int lru_host_call(xcg_ctx* c, uint64_t hash, const uint8_t* in_seg, uint8_t* out
         hipStreamSynchronize(nullptr) != hipSuccess)
       rc = XCG_EHIP;
   } while (0);
-  (void)hipFree(m);
   return rc;
 }
 }  // namespace
 
 namespace {
-uint64_t host_seg_hash(const uint8_t* w) {   // XCodecHash::hash, xcodec/xcodec_hash.h:166-174
-  uint32_t s1 = 0, s2 = 0, b1 = 0, b2 = 0;
-  for (uint32_t k = 0; k < XCG_SEGMENT_LENGTH; ++k) {
-    s1 += (uint32_t)w[k] + 1u;
-    s2 += s1;
-    b1 += w[k] ? (uint32_t)__builtin_ctz(w[k]) + 1u : 0u;
-    b2 += b1;
-  }
-  return ((uint64_t)((b1 << 16) + b2) << 36) + (uint64_t)((s1 << 20) + s2);
-}
-
 // Single-segment host calls on a pair: a one-op decode batch that leaves the
 // BACKREF window alone.  A lookup is <REF hash> (XCodecCachePair::lookup, with
 // its LRU use / disk touch / promotion, xcodec_cache.h:208-230); an enter is
@@ -1050,7 +993,7 @@ int xcg_cache_lookup_host(xcg_ctx* c, uint64_t hash, uint8_t* seg_out) {
 int xcg_cache_enter_host(xcg_ctx* c, uint64_t hash, const uint8_t* seg) {
   if (!c || !seg) return XCG_EINVAL;
   if (c->pair) {
-    if (host_seg_hash(seg) != hash) return XCG_EINVAL;   // (a pair names a segment by its own hash)
+    if (xcg::host_seg_hash(seg) != hash) return XCG_EINVAL;   // (a pair names a segment by its own hash)
     int32_t found = 0;
     return pair_host_call(c, hash, seg, nullptr, &found);
   }
@@ -1201,6 +1144,7 @@ XcgStreamArgs stream_args(xcg_ctx* c, const uint8_t* d_in, const uint64_t* d_chu
   a.s_qcnt = b.s_qcnt; a.s_qkeys = b.s_qkeys;
   if (c->pair || c->bounded) {
     a.ev = b.ev; a.nev = b.nev; a.maxe = b.maxe;
+    a.ev_base = b.ev_base; a.enter_base = b.enter_base; a.ev_slot = b.ev_slot; a.ev_time = b.ev_time;
     a.eo = b.eo; a.bad_t = b.bad_t; a.bad_hi = b.bad_hi; a.bslot = b.bslot; a.b_count = b.b_count;
     a.b_slots = b.b_slots; a.b_ev = b.b_ev; a.b_eo = b.b_eo; a.b_hits = b.b_hits; a.b_cnt = b.b_cnt;
     a.b_out = b.b_out; a.b_stride = b.b_stride; a.splice = b.splice;
@@ -1234,10 +1178,6 @@ int encode_batch_impl(xcg_ctx* c, int semantics, const uint8_t* d_in, const uint
     if (c->pair) {
       rc = xcg_pair_encode_stream(&a, c->pair, &rounds, (hipStream_t)stream);
     } else if (c->bounded) {
-      c->lru.ev_base = c->bs.ev_base;
-      c->lru.enter_base = c->bs.enter_base;
-      c->lru.evslot = c->bs.ev_slot;
-      c->lru.evtime = c->bs.ev_time;
       rc = xcg_lru_encode_stream(&a, &c->lru, &rounds, (hipStream_t)stream);
     } else {
       rc = xcg_launch_encode_stream(&a, &rounds, (hipStream_t)stream);
@@ -1283,7 +1223,8 @@ int xcg_encode_host(xcg_ctx* c, int semantics, const uint8_t* h_in, uint64_t in_
   }
   DeviceGuard g(c->device);
   // staging (kept by the context): [off n][oo n][ol n][len n] | input | output slots
-  const size_t meta = align256(28ull * n), inb = align256(in_len ? in_len : 1), outb = align256(out_cap ? out_cap : 1);
+  const size_t meta = align_up(28ull * n, 256), inb = align_up(in_len ? in_len : 1, 256),
+               outb = align_up(out_cap ? out_cap : 1, 256);
   int rc = ensure_stage(c, meta + inb + outb, meta + inb + outb);
   if (rc != XCG_OK) return rc;
   uint8_t* hm = c->stage_h;
@@ -1337,14 +1278,14 @@ int xcg_encode_call(xcg_ctx* c, const uint8_t* h_in, uint32_t len, uint8_t* h_ou
   // staging: device [off 8][oo 8][ol 8][len 4] | input | output slot;
   //          host   the same head, then [ndecl 4][nev 4] | decl rows | event rows | output
   const uint64_t bound = xcg_encode_bound(len);
-  const size_t inb = align256(len), outb = align256(bound);
-  const size_t rows_d = align256(16ull * maxd);
+  const size_t inb = align_up(len, 256), outb = align_up(bound, 256);
+  const size_t rows_d = align_up(16ull * maxd, 256);
   size_t rows_e = 0;
   if (refs) {
     int rc0 = ensure_cache(c);
     if (rc0 == XCG_OK) rc0 = ensure_scratch(c, 1, maxd);
     if (rc0 != XCG_OK) return rc0;
-    rows_e = align256(16ull * c->bs.maxe);
+    rows_e = align_up(16ull * c->bs.maxe, 256);
   }
   int rc = ensure_stage(c, 256 + inb + outb, 256 + inb + 256 + rows_d + rows_e + outb);
   if (rc != XCG_OK) return rc;
@@ -1577,7 +1518,8 @@ int xcg_decode_host(xcg_ctx* c, const uint8_t* h_enc, uint64_t enc_len, const ui
   }
   DeviceGuard g(c->device);
   // staging (kept by the context): [off n][oo n][ol n][cons n][len n][status n] | input | output
-  const size_t meta = align256(40ull * n), inb = align256(enc_len ? enc_len : 1), outb = align256(out_cap ? out_cap : 1);
+  const size_t meta = align_up(40ull * n, 256), inb = align_up(enc_len ? enc_len : 1, 256),
+               outb = align_up(out_cap ? out_cap : 1, 256);
   int rc = ensure_stage(c, meta + inb + outb, meta + inb + outb);
   if (rc != XCG_OK) return rc;
   uint8_t* hm = c->stage_h;
@@ -1675,21 +1617,19 @@ int decode_call_zc(xcg_ctx* c, const uint8_t* h_in, uint32_t len, uint8_t* h_out
                    uint32_t rw, uint64_t* h_out_len, uint64_t* h_consumed, int32_t* h_status, uint64_t* h_unknown,
                    uint32_t unknown_cap, uint32_t* h_nunknown, uint64_t* h_extract_hash, uint32_t extract_cap,
                    uint32_t* h_nextract) {
-  const size_t inb = align256(len), outb = align256(out_cap ? out_cap : 1), resb = align256(8ull * rw);
+  const size_t inb = align_up(len, 256), outb = align_up(out_cap ? out_cap : 1, 256), resb = align_up(8ull * rw, 256);
   const size_t need = 256 + inb + outb + resb;
   if (need > c->zc_cap) {
-    if (c->zc_h) {
-      (void)hipStreamSynchronize(c->call_st);
-      (void)hipHostFree(c->zc_h);
-    }
+    if (c->zc_h) (void)hipStreamSynchronize(c->call_st);
+    c->mem_call.release(c->zc_h);
     c->zc_h = nullptr;
     c->zc_cap = 0;
     const size_t want = need + need / 2;
-    if (hipHostMalloc(&c->zc_h, want, hipHostMallocCoherent) != hipSuccess) return XCG_ENOMEM;
+    if (!c->mem_call.pinned(&c->zc_h, want, true)) return XCG_ENOMEM;
     c->zc_cap = want;
     memset(c->zc_h, 0, 256);
   }
-  const size_t scr = align256(xcg_decode_small_scratch(ops_cap));
+  const size_t scr = align_up(xcg_decode_small_scratch(ops_cap), 256);
   int rc = ensure_stage(c, scr, 0);                  // (device scratch: the op lists)
   if (rc != XCG_OK) return rc;
   uint8_t* hz = c->zc_h;
@@ -1775,10 +1715,10 @@ int xcg_decode_call(xcg_ctx* c, const uint8_t* h_in, uint32_t len, uint8_t* h_ou
     }
     // device: input | output | results | op lists;  host: input | output | results (one D2H brings
     // both back; the results' last word is the context's sticky word)
-    const size_t inb = align256(len), outb = align256(out_cap ? out_cap : 1), resb = align256(8ull * rw);
-    const size_t scr = align256(xcg_decode_small_scratch(ops_cap));
+    const size_t inb = align_up(len, 256), outb = align_up(out_cap ? out_cap : 1, 256), resb = align_up(8ull * rw, 256);
+    const size_t scr = align_up(xcg_decode_small_scratch(ops_cap), 256);
     const uint32_t nph = xcg_decode_small_phases();
-    const size_t timb = dphase_on() ? align256(8ull * nph) : 0;
+    const size_t timb = dphase_on() ? align_up(8ull * nph, 256) : 0;
     rc = ensure_stage(c, inb + outb + resb + scr + timb, inb + outb + resb);
     if (rc != XCG_OK) return rc;
     uint8_t* dm = c->stage_d;

@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "xcg_devmem.h"
+
 struct xcg_ctx;
 
 // Device view of a context's persistent segment cache (layout: xcg_cache.h):
@@ -77,6 +79,10 @@ struct XcgStreamArgs {
   void* ev;
   uint32_t* nev;
   uint32_t maxe;
+  uint32_t* ev_base;     // [n + 1], [n + 1]: the LRU pass's row and enter bases
+  uint32_t* enter_base;
+  uint32_t* ev_slot;     // [n * maxe]: each reference's pool slot / LRU time
+  uint64_t* ev_time;
   int no_commit;
   int keep_decls;        // start from the declaration lists already in decl/ndecl
   int need_given;        // (keep_decls) round 1 parses only the chunks flagged in need[]
@@ -124,8 +130,10 @@ struct XcgStreamArgs {
 // the conservative flag), a table of twice that, a 32 KiB blocked Bloom filter.
 constexpr uint32_t XCG_VERIFY_A_LIMIT = 8192, XCG_VERIFY_A_CAP = 16384, XCG_VERIFY_A_WORDS = 8192;
 
-// Bounded cache (xcg_lru.hip): device LRU state of a context.
+// Bounded cache (xcg_lru.hip): device LRU state of a context.  Persistent
+// arrays only: what belongs to one batch travels in its LruBatch.
 struct XcgLruState {
+  xcg::DevMem* mem;       // the context's owner of these arrays (host)
   uint32_t C;             // memory_cache_limit_ in segments (= pool slots)
   uint64_t* skey;         // [C] key of the entry in pool slot s
   uint64_t* lastref;      // [C] LRU time of its last enter / lookup
@@ -137,10 +145,6 @@ struct XcgLruState {
   uint64_t* tau;
   uint32_t* alive;
   uint32_t* freel;
-  uint32_t* evslot;       // per reference of the batch (scratch)
-  uint64_t* evtime;
-  uint32_t* ev_base;      // [n + 1]
-  uint32_t* enter_base;   // [n + 1]
   uint32_t* tot;          // [16]
   uint32_t* h_tot;        // pinned [16]
   uint64_t clock;         // LRU time base of the next batch (host)
@@ -171,6 +175,12 @@ struct LruBatch {
   uint64_t ev_bound;      // upper bound of the batch's references (sizes the scans)
   uint32_t* bad_t;        // (encoder, optional) per chunk earliest / latest contradicted lookup time
   uint32_t* bad_hi;
+  // the pass's scratch, the caller's for the batch: per reference its pool slot
+  // and LRU time; per chunk its first row and first enter
+  uint32_t* evslot;
+  uint64_t* evtime;
+  uint32_t* ev_base;      // [n + 1]
+  uint32_t* enter_base;   // [n + 1]
 };
 
 // XCodecCachePair of a bounded memory primary and a disk secondary (xcg_pair.hip).

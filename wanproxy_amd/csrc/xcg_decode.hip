@@ -1780,6 +1780,8 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
   }
   // Bounded cache: classify every op against the eviction times until they
   // agree (xcg_lru.hip); the passes below then see the cache as it evolves.
+  // (the call's stream-ordered temporaries: each freed on `stream` at every exit)
+  StreamTemp lru_tmp(stream), pair_tmp(stream), dfull_tmp(stream), occ_tmp(stream);
   uint8_t* lru_mem = nullptr;
   LruBatch lb{};
   uint4 *raw = nullptr, *evs = nullptr;
@@ -1790,18 +1792,18 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
     // raw ops, classified ops, declaration rows | evtime | evslot, per-chunk
     // counts, bases, flags
     const uint64_t bytes = 32 * m + 16ull * n * a->maxd + 8 * m + 4 * m + 20ull * (n + 1) + 64;
-    if (hipMallocAsync((void**)&lru_mem, bytes, stream) != hipSuccess) return -5;
+    if (!lru_tmp.alloc(&lru_mem, bytes)) return -5;
     raw = (uint4*)lru_mem;
     evs = raw + m;
     uint4* drow = evs + m;
-    L->evtime = (uint64_t*)(drow + (uint64_t)n * a->maxd);
-    L->evslot = (uint32_t*)(L->evtime + m);
-    uint32_t* nev32 = L->evslot + m;
+    lb.evtime = (uint64_t*)(drow + (uint64_t)n * a->maxd);
+    lb.evslot = (uint32_t*)(lb.evtime + m);
+    uint32_t* nev32 = lb.evslot + m;
     uint32_t* nd32 = nev32 + (n + 1);
     uint32_t* need = nd32 + (n + 1);
-    L->ev_base = need + (n + 1);
-    L->enter_base = L->ev_base + (n + 1);
-    uint64_t* blk = (uint64_t*)(((uintptr_t)(L->enter_base + n + 1) + 15) & ~(uintptr_t)15);
+    lb.ev_base = need + (n + 1);
+    lb.enter_base = lb.ev_base + (n + 1);
+    uint64_t* blk = (uint64_t*)(((uintptr_t)(lb.enter_base + n + 1) + 15) & ~(uintptr_t)15);
     uint32_t* changes = (uint32_t*)(blk + 1);
     lb.n = n; lb.in = a->in; lb.chunk_off = a->chunk_off;
     lb.decl = drow; lb.ndecl = nd32; lb.maxd = a->maxd;
@@ -1810,27 +1812,23 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
     lb.g = a->g;
     lb.status = a->status;
     lb.ev_bound = m;
-    auto fail = [&](int rc) {
-      (void)hipFreeAsync(lru_mem, stream);
-      return rc;
-    };
     hipLaunchKernelGGL(dec_ops_kernel, grid, block, 0, stream, p, raw);
-    if (xcg_lru_reset_times(L, stream)) return fail(-5);
+    if (xcg_lru_reset_times(L, stream)) return -5;
     p.ptime = L->ptime;
     uint64_t blockp = ~0ull;
     bool agreed = false;
     for (int pass = 0; pass < 64 && !agreed; ++pass) {
       if (hipMemsetAsync(blk, 0xFF, 8, stream) != hipSuccess || hipMemsetAsync(changes, 0, 4, stream) != hipSuccess)
-        return fail(-5);
+        return -5;
       hipLaunchKernelGGL(dec_classify_kernel<false>, grid, block, 0, stream, p, (const uint4*)raw, evs, nev32, drow, nd32,
                          a->maxd, blockp, blk, changes, pass == 0 ? 1 : 0);
-      if (xcg_lru_times(&lb, L, stream)) return fail(-5);   // (synchronises)
+      if (xcg_lru_times(&lb, L, stream)) return -5;   // (synchronises)
       if (hipMemcpyAsync(a->h_scratch + 8, blk, 16, hipMemcpyDeviceToHost, stream) != hipSuccess ||
           hipStreamSynchronize(stream) != hipSuccess)
-        return fail(-5);
+        return -5;
       const uint64_t nb = a->h_scratch[8];
       const uint32_t nchg = (uint32_t)a->h_scratch[9];
-      if ((uint64_t)L->h_tot[1] + L->h_tot[8] > L->C) return fail(-95);   // enters + persistent lookups > limit
+      if ((uint64_t)L->h_tot[1] + L->h_tot[8] > L->C) return -95;   // enters + persistent lookups > limit
       if (getenv("XCG_LRU_DEBUG"))
         fprintf(stderr, "lru-dec: n %u pass %d enters %u evict %u live %u hits %u changes %u block %llx -> %llx\n", n,
                 pass, L->h_tot[1], L->h_tot[2], L->h_tot[3], L->h_tot[8], nchg, (unsigned long long)blockp,
@@ -1838,7 +1836,7 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
       agreed = nchg == 0 && nb == blockp;
       blockp = nb;
     }
-    if (!agreed) return fail(-75);
+    if (!agreed) return -75;
   }
   // Pair: classify every op against ptime (the time a hash leaves both
   // levels), replay the classified ops through the pair's policy on the host
@@ -1851,11 +1849,7 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
     if (xcg_pair_decode_begin(a->pair, stream)) return -5;
     const uint64_t m = ndecl ? ndecl : 1;
     const uint64_t bytes = 32 * m + 16ull * n * a->maxd + 8ull * (n + 1) + 64;
-    if (hipMallocAsync((void**)&pair_mem, bytes, stream) != hipSuccess) return -5;
-    auto fail = [&](int rc) {
-      (void)hipFreeAsync(pair_mem, stream);
-      return rc;
-    };
+    if (!pair_tmp.alloc(&pair_mem, bytes)) return -5;
     raw = (uint4*)pair_mem;
     evs = raw + m;
     prow = evs + m;
@@ -1869,14 +1863,14 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
     bool agreed = false;
     for (int pass = 0; pass < 64 && !agreed; ++pass) {
       if (hipMemsetAsync(blk, 0xFF, 8, stream) != hipSuccess || hipMemsetAsync(changes, 0, 4, stream) != hipSuccess)
-        return fail(-5);
+        return -5;
       hipLaunchKernelGGL(dec_classify_kernel<true>, grid, block, 0, stream, p, (const uint4*)raw, evs, nev32, prow, nd32,
                          a->maxd, blockp, blk, changes, 1);
-      if (hipMemcpyAsync(a->h_scratch + 8, blk, 8, hipMemcpyDeviceToHost, stream) != hipSuccess) return fail(-5);
+      if (hipMemcpyAsync(a->h_scratch + 8, blk, 8, hipMemcpyDeviceToHost, stream) != hipSuccess) return -5;
       int same = 0;
       const PairGpu G = pair_gpu(a, prow);
       const int prc = xcg_pair_decode_pass(a->pair, &G, evs, p.decl_base, p.n_decl, n, ndecl, a->maxd, &same, stream);
-      if (prc) return fail(prc);
+      if (prc) return prc;
       const uint64_t nb = a->h_scratch[8];
       if (getenv("XCG_PAIR_DEBUG"))
         fprintf(stderr, "pair-dec: n %u pass %d same %d block %llx -> %llx\n", n, pass, same,
@@ -1884,12 +1878,12 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
       agreed = same && nb == blockp;
       blockp = nb;
     }
-    if (!agreed) return fail(-75);
+    if (!agreed) return -75;
   }
   uint4* dfull = nullptr;
   if (nbref > 0 && ndecl > 0) {
     // BACKREFs present: records of every declare (rare; never made by XCodecEncoder)
-    if (hipMallocAsync((void**)&dfull, 16ull * ndecl, stream) != hipSuccess) return -5;
+    if (!dfull_tmp.alloc(&dfull, 16ull * ndecl)) return -5;
     p.D = dfull;
     p.D_lo = 0;
     p.D_tail = false;
@@ -1908,10 +1902,8 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
   if (hipMemcpyAsync(a->h_scratch, a->scratch, 24, hipMemcpyDeviceToHost, stream) != hipSuccess ||
       hipMemcpyAsync(a->h_scratch + 6, a->nunknown, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
       hipMemcpyAsync(a->h_scratch + 10, a->status, 4, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-      hipStreamSynchronize(stream) != hipSuccess) {
-    if (dfull) (void)hipFreeAsync(dfull, stream);
+      hipStreamSynchronize(stream) != hipSuccess)
     return -5;
-  }
   const uint32_t nconf = (uint32_t)(a->h_scratch[6] >> 32);
   a->h_scratch[13] = nconf;
   if (a->h_scratch[10] & (1u << 9)) {
@@ -1919,21 +1911,13 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
     a->h_scratch[11] = a->h_scratch[10] & ~(uint64_t)(1u << 9);
     (void)hipMemcpyAsync(a->status, a->h_scratch + 11, 4, hipMemcpyHostToDevice, stream);
     (void)hipStreamSynchronize(stream);
-    if (dfull) (void)hipFreeAsync(dfull, stream);
-    if (lru_mem) (void)hipFreeAsync(lru_mem, stream);
-    if (pair_mem) (void)hipFreeAsync(pair_mem, stream);
     return -95;
   }
   *total_out = a->h_scratch[0];
   *block_pos_out = a->h_scratch[1];
   *berr_pos_out = a->h_scratch[2];
   *nunknown_out = (uint32_t)(a->h_scratch[6] & 0xFFFFFFFFu);
-  if (*total_out > a->out_cap) {
-    if (dfull) (void)hipFreeAsync(dfull, stream);
-    if (lru_mem) (void)hipFreeAsync(lru_mem, stream);
-    if (pair_mem) (void)hipFreeAsync(pair_mem, stream);
-    return -75;
-  }
+  if (*total_out > a->out_cap) return -75;
   // Name reuse (hashes whose EXTRACTs differ; unbounded contexts only get
   // here): their occurrences sorted by (hash, position) -- a stable sort by
   // position, then by hash -- for the REUSE kernels' binary search.
@@ -1944,28 +1928,19 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
     size_t tmp1 = 0, tmp2 = 0;
     if (rocprim::radix_sort_pairs(nullptr, tmp1, v0, v1, k0, k1, m, 0, 64, stream) != hipSuccess ||
         rocprim::radix_sort_pairs(nullptr, tmp2, k1, k0, v1, v0, m, 0, 64, stream) != hipSuccess ||
-        hipMallocAsync((void**)&occ_mem, 32ull * m + 256 + (tmp1 > tmp2 ? tmp1 : tmp2), stream) != hipSuccess) {
-      if (dfull) (void)hipFreeAsync(dfull, stream);
+        !occ_tmp.alloc(&occ_mem, 32ull * m + 256 + (tmp1 > tmp2 ? tmp1 : tmp2)))
       return -5;
-    }
     k0 = (uint64_t*)occ_mem; k1 = k0 + m; v0 = k1 + m; v1 = v0 + m;
     void* tmp = (void*)(((uintptr_t)(v1 + m) + 255) & ~(uintptr_t)255);
     uint32_t* nocc = a->nunknown + 2;
-    if (hipMemsetAsync(occ_mem, 0xFF, 32ull * m, stream) != hipSuccess) {
-      (void)hipFreeAsync(occ_mem, stream);
-      if (dfull) (void)hipFreeAsync(dfull, stream);
-      return -5;
-    }
+    if (hipMemsetAsync(occ_mem, 0xFF, 32ull * m, stream) != hipSuccess) return -5;
     hipLaunchKernelGGL(dec_occ_owner_kernel, dim3((unsigned)(((uint64_t)a->x_mask + 256) / 256)), dim3(256), 0, stream,
                        p, k0, v0, nocc, m);
     hipLaunchKernelGGL(dec_occ_dup_kernel, dim3((unsigned)((ndup + 255) / 256)), dim3(256), 0, stream, p, (uint32_t)ndup,
                        k0, v0, nocc, m);
     if (rocprim::radix_sort_pairs(tmp, tmp1, v0, v1, k0, k1, m, 0, 64, stream) != hipSuccess ||
-        rocprim::radix_sort_pairs(tmp, tmp2, k1, k0, v1, v0, m, 0, 64, stream) != hipSuccess) {
-      (void)hipFreeAsync(occ_mem, stream);
-      if (dfull) (void)hipFreeAsync(dfull, stream);
+        rocprim::radix_sort_pairs(tmp, tmp2, k1, k0, v1, v0, m, 0, 64, stream) != hipSuccess)
       return -5;
-    }
     p.occ_key = k0;
     p.occ_pos = v0;
     p.nocc = m;
@@ -2003,15 +1978,12 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
     // the classification's declaration rows give each new entry's bytes
     const PairGpu G = pair_gpu(a, prow);
     const int crc = xcg_pair_decode_commit(a->pair, &G, stream);
-    (void)hipFreeAsync(pair_mem, stream);
-    if (dfull) (void)hipFreeAsync(dfull, stream);
     if (crc) return crc;
     return hipGetLastError() == hipSuccess ? 0 : -5;
   }
   if (a->lru) {
     hipLaunchKernelGGL(dec_replace_kernel, grid, block, 0, stream, p, (const uint4*)raw, (const uint4*)evs, a->g.pool);
     const int crc = xcg_lru_commit(&lb, a->lru, stream);
-    (void)hipFreeAsync(lru_mem, stream);
     if (crc) return crc;
   } else {
     const uint64_t slots = (uint64_t)a->x_mask + 1;
@@ -2024,8 +1996,6 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
                          a->g.pool, a->g.nseg, a->g.seg_cap, fs);
     seg3.end();
   }
-  if (occ_mem) (void)hipFreeAsync(occ_mem, stream);
-  if (dfull) (void)hipFreeAsync(dfull, stream);
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

@@ -47,6 +47,7 @@
 
 #include "../../include/xcgpu.h"
 #include "xcg_device.h"
+#include "xcg_devmem.h"
 #include "xcg_stored_plan.h"
 
 namespace xcg {
@@ -1691,6 +1692,7 @@ __global__ __launch_bounds__(256) void zs_commit_kernel(ZArgs a) {
 using namespace xcg::zd;
 
 struct xcg_zdeflate {
+  xcg::DevMem mem;                 // every buffer below
   int device = 0, level = 6;
   uint32_t nstreams = 0;
   ZState* st = nullptr;
@@ -1718,24 +1720,7 @@ struct xcg_zdeflate {
 };
 
 namespace {
-int grow(void** p, size_t* cap, size_t want, bool pinned) {
-  if (*cap >= want) return XCG_OK;
-  size_t n = std::max(want, *cap * 3 / 2);
-  if (*p) {
-    if (pinned) (void)hipHostFree(*p);
-    else (void)hipFree(*p);
-    *p = nullptr;
-  }
-  hipError_t e = pinned ? hipHostMalloc(p, n) : hipMalloc(p, n);
-  if (e != hipSuccess) {
-    *cap = 0;
-    *p = nullptr;
-    return XCG_ENOMEM;
-  }
-  *cap = n;
-  return XCG_OK;
-}
-inline size_t al(size_t v, size_t a) { return (v + a - 1) / a * a; }
+using xcg::align_up;
 ZState fresh_state() {   // deflateInit
   ZState s;
   memset(&s, 0, sizeof s);
@@ -1756,21 +1741,21 @@ int xcg_zdeflate_create(int device, int level, uint32_t nstreams, xcg_zdeflate**
   z->device = device;
   z->level = level;
   z->nstreams = nstreams;
-  if (hipMalloc(&z->st, sizeof(ZState) * nstreams) != hipSuccess ||
-      hipMalloc(&z->hist, (size_t)WSIZE * (level == 0 ? 2 : 1) * nstreams) != hipSuccess ||
+  auto fail = [&](int rc) {
+    xcg_zdeflate_destroy(z);
+    return rc;
+  };
+  if (!(z->mem.dev(&z->st, sizeof(ZState) * nstreams) &&
+        z->mem.dev(&z->hist, (size_t)WSIZE * (level == 0 ? 2 : 1) * nstreams)) ||
       hipEventCreateWithFlags(&z->done, hipEventDisableTiming) != hipSuccess ||
-      (level < 4 && (hipMalloc(&z->ring, (size_t)WSIZE / 8 * nstreams) != hipSuccess ||
-                     hipMemset(z->ring, 0, (size_t)WSIZE / 8 * nstreams) != hipSuccess))) {
-    delete z;
-    return XCG_ENOMEM;
-  }
+      (level < 4 && (!z->mem.dev(&z->ring, (size_t)WSIZE / 8 * nstreams) ||
+                     hipMemset(z->ring, 0, (size_t)WSIZE / 8 * nstreams) != hipSuccess)))
+    return fail(XCG_ENOMEM);
   z->h_init.assign(nstreams, fresh_state());
   if (level == 0) z->splan.assign(nstreams, StoredPlan());
   if (hipMemcpy(z->st, z->h_init.data(), sizeof(ZState) * nstreams, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemset(z->hist, 0, (size_t)WSIZE * nstreams) != hipSuccess) {
-    delete z;
-    return XCG_EHIP;
-  }
+      hipMemset(z->hist, 0, (size_t)WSIZE * nstreams) != hipSuccess)
+    return fail(XCG_EHIP);
   *out = z;
   return XCG_OK;
 }
@@ -1779,16 +1764,8 @@ void xcg_zdeflate_destroy(xcg_zdeflate* z) {
   if (!z) return;
   (void)hipSetDevice(z->device);
   if (z->done) (void)hipEventSynchronize(z->done);
-  (void)hipFree(z->st);
-  (void)hipFree(z->hist);
-  (void)hipFree(z->ring);
-  if (z->h_changed) (void)hipHostFree(z->h_changed);
-  if (z->hs_h) (void)hipHostFree(z->hs_h);
-  (void)hipFree(z->hs_d);
+  z->mem.release_all();
   if (z->hst) (void)hipStreamDestroy(z->hst);
-  (void)hipFree(z->scratch);
-  (void)hipFree(z->meta);
-  if (z->h_meta) (void)hipHostFree(z->h_meta);
   if (z->done) (void)hipEventDestroy(z->done);
   delete z;
 }
@@ -1841,12 +1818,14 @@ int stored_batch(xcg_zdeflate* z, const uint8_t* d_in, const uint64_t* h_in_off,
     made32[i] = (uint32_t)made;
     for (size_t k = first; k < pieces.size(); k++) pieces[k].call = i;
   }
-  size_t m_calls = 0, m_pc = al(sizeof(ZCall) * n, 256), m_len = al(m_pc + sizeof(ZPiece) * pieces.size(), 256),
-         m_dl = al(m_len + 4ull * n, 256), m_end = al(m_dl + 8ull * n, 256);
+  size_t m_calls = 0, m_pc = align_up(sizeof(ZCall) * n, 256), m_len = align_up(m_pc + sizeof(ZPiece) * pieces.size(), 256),
+         m_dl = align_up(m_len + 4ull * n, 256), m_end = align_up(m_dl + 8ull * n, 256);
   if (hipEventSynchronize(z->done) != hipSuccess) return XCG_EHIP;
   const size_t r_res = sizeof(ZCallRes) * n;
-  if (grow((void**)&z->scratch, &z->scratch_cap, al(r_res, 256), false)) return XCG_ENOMEM;
-  if (grow(&z->meta, &z->meta_cap, m_end, false) || grow(&z->h_meta, &z->h_meta_cap, m_end, true)) return XCG_ENOMEM;
+  if (!z->mem.grow_bytes(&z->scratch, &z->scratch_cap, align_up(r_res, 256), xcg::MEM_DEV)) return XCG_ENOMEM;
+  if (!z->mem.grow_bytes(&z->meta, &z->meta_cap, m_end, xcg::MEM_DEV) ||
+      !z->mem.grow_bytes(&z->h_meta, &z->h_meta_cap, m_end, xcg::MEM_PINNED))
+    return XCG_ENOMEM;
   uint8_t* hm = (uint8_t*)z->h_meta;
   memcpy(hm + m_calls, calls.data(), sizeof(ZCall) * n);
   if (!pieces.empty()) memcpy(hm + m_pc, pieces.data(), sizeof(ZPiece) * pieces.size());
@@ -1909,11 +1888,11 @@ int xcg_zdeflate_batch_seg(xcg_zdeflate* z, const uint8_t* d_in, const uint64_t*
     c.len = h_len[i];
     c.stream = h_stream[i];
     c.x_off = xo;
-    xo += al((size_t)WSIZE + c.len + XPAD, 256);
+    xo += align_up((size_t)WSIZE + c.len + XPAD, 256);
     c.m_off = mo;                                 // (deflate_fast masks: one bit per X index)
-    mo += fast ? al(((size_t)WSIZE + c.len + 64) / 32 + 1, 64) : 0;
+    mo += fast ? align_up(((size_t)WSIZE + c.len + 64) / 32 + 1, 64) : 0;
     c.t_off = to;                                 // (parsed positions: up to DMAX left by the last call)
-    to += al((size_t)c.len + DMAX + 1, 64);
+    to += align_up((size_t)c.len + DMAX + 1, 64);
     c.blk_off = bo;
     c.blk_cap = (c.len + DMAX) / SYMS_PER_BLOCK + 2;
     bstart[i] = bo;
@@ -1924,18 +1903,20 @@ int xcg_zdeflate_batch_seg(xcg_zdeflate* z, const uint8_t* d_in, const uint64_t*
   bstart[n] = bo;
   const uint32_t mtiles = mstart[n], groups = gstart[n];
   // scratch layout
-  size_t o_X = 0, o_d16 = al(o_X + xo, 256), o_pk = al(o_d16 + 2 * xo, 256), o_tf = al(o_pk + 4 * xo, 256),
-         o_tq = al(o_tf + 4 * to, 256),
-         o_sym = al(o_tq + 4 * to, 256), o_blk = al(o_sym + 4 * to, 256),
-         o_tab = al(o_blk + sizeof(ZBlock) * bo, 256), o_res = al(o_tab + 4ull * TAB_WORDS * bo, 256),
-         o_ma = al(o_res + sizeof(ZCallRes) * n, 256), o_mb = al(o_ma + 4 * mo, 256), o_chg = al(o_mb + 4 * mo, 256),
-         o_end = al(o_chg + 4ull * n, 256);
+  size_t o_X = 0, o_d16 = align_up(o_X + xo, 256), o_pk = align_up(o_d16 + 2 * xo, 256), o_tf = align_up(o_pk + 4 * xo, 256),
+         o_tq = align_up(o_tf + 4 * to, 256),
+         o_sym = align_up(o_tq + 4 * to, 256), o_blk = align_up(o_sym + 4 * to, 256),
+         o_tab = align_up(o_blk + sizeof(ZBlock) * bo, 256), o_res = align_up(o_tab + 4ull * TAB_WORDS * bo, 256),
+         o_ma = align_up(o_res + sizeof(ZCallRes) * n, 256), o_mb = align_up(o_ma + 4 * mo, 256), o_chg = align_up(o_mb + 4 * mo, 256),
+         o_end = align_up(o_chg + 4ull * n, 256);
   // the previous batch may still read the scratch
   if (hipEventSynchronize(z->done) != hipSuccess) return XCG_EHIP;
-  if (grow((void**)&z->scratch, &z->scratch_cap, o_end, false)) return XCG_ENOMEM;
-  size_t m_calls = 0, m_ms = al(sizeof(ZCall) * n, 256), m_gs = al(m_ms + 4ull * (n + 1), 256),
-         m_bs = al(m_gs + 4ull * (n + 1), 256), m_end = al(m_bs + 4ull * (n + 1), 256);
-  if (grow(&z->meta, &z->meta_cap, m_end, false) || grow(&z->h_meta, &z->h_meta_cap, m_end, true)) return XCG_ENOMEM;
+  if (!z->mem.grow_bytes(&z->scratch, &z->scratch_cap, o_end, xcg::MEM_DEV)) return XCG_ENOMEM;
+  size_t m_calls = 0, m_ms = align_up(sizeof(ZCall) * n, 256), m_gs = align_up(m_ms + 4ull * (n + 1), 256),
+         m_bs = align_up(m_gs + 4ull * (n + 1), 256), m_end = align_up(m_bs + 4ull * (n + 1), 256);
+  if (!z->mem.grow_bytes(&z->meta, &z->meta_cap, m_end, xcg::MEM_DEV) ||
+      !z->mem.grow_bytes(&z->h_meta, &z->h_meta_cap, m_end, xcg::MEM_PINNED))
+    return XCG_ENOMEM;
   uint8_t* hm = (uint8_t*)z->h_meta;
   memcpy(hm + m_calls, calls.data(), sizeof(ZCall) * n);
   memcpy(hm + m_ms, mstart.data(), 4ull * (n + 1));
@@ -1988,7 +1969,7 @@ int xcg_zdeflate_batch_seg(xcg_zdeflate* z, const uint8_t* d_in, const uint64_t*
     // (round 0: all), build the chains and the match table from the guess, parse,
     // and repeat with the parse's hashed positions until they reproduce the guess
     // (the correct prefix grows every round, so this ends).
-    if (grow((void**)&z->h_changed, &z->h_changed_cap, 4ull * n, true)) return XCG_ENOMEM;
+    if (!z->mem.grow_bytes(&z->h_changed, &z->h_changed_cap, 4ull * n, xcg::MEM_PINNED)) return XCG_ENOMEM;
     const unsigned mgrid = (unsigned)std::min<size_t>(4096, (mo + 255) / 256 + 1);
     hipLaunchKernelGGL(zd_mfill_kernel, dim3(mgrid), dim3(256), 0, st, mA, mB, (uint64_t)mo);
     uint32_t rounds = 0;
@@ -2047,12 +2028,13 @@ int xcg_zdeflate_host(xcg_zdeflate* z, const uint8_t* h_in, const uint64_t* h_in
   for (uint32_t i = 0; i < n; i++) {
     in_end = std::max(in_end, h_in_off[i] + h_len[i]);
     doff[i] = out_end;
-    out_end += al(xcg_zdeflate_bound(h_len[i]), 4);
+    out_end += align_up(xcg_zdeflate_bound(h_len[i]), 4);
   }
   // staging: [in][out][out_len n][deliver n]
-  const size_t o_out = al(in_end + 1, 256), o_len = al(o_out + out_end, 256), o_dl = al(o_len + 4ull * n, 256),
-               o_end = al(o_dl + 8ull * n, 256);
-  if (grow((void**)&z->hs_h, &z->hs_hcap, o_end, true) || grow((void**)&z->hs_d, &z->hs_dcap, o_end, false))
+  const size_t o_out = align_up(in_end + 1, 256), o_len = align_up(o_out + out_end, 256), o_dl = align_up(o_len + 4ull * n, 256),
+               o_end = align_up(o_dl + 8ull * n, 256);
+  if (!z->mem.grow_bytes(&z->hs_h, &z->hs_hcap, o_end, xcg::MEM_PINNED) ||
+      !z->mem.grow_bytes(&z->hs_d, &z->hs_dcap, o_end, xcg::MEM_DEV))
     return XCG_ENOMEM;
   if (in_end) memcpy(z->hs_h, h_in, in_end);
   if (in_end && hipMemcpyAsync(z->hs_d, z->hs_h, in_end, hipMemcpyHostToDevice, z->hst) != hipSuccess) return XCG_EHIP;

@@ -27,6 +27,7 @@
 
 #include "../../include/xcgpu.h"
 #include "xcg_device.h"
+#include "xcg_devmem.h"
 
 namespace xcg {
 namespace zi {
@@ -1418,6 +1419,7 @@ __global__ __launch_bounds__(64 * AW) void zi_adler_kernel(IArgs a) {
 using namespace xcg::zi;
 
 struct xcg_zinflate {
+  xcg::DevMem mem;                 // every buffer below
   int device = 0;
   uint32_t nstreams = 0;
   IState* st = nullptr;
@@ -1438,24 +1440,7 @@ struct xcg_zinflate {
 };
 
 namespace {
-int igrow(void** p, size_t* cap, size_t want, bool pinned) {
-  if (*cap >= want) return XCG_OK;
-  size_t n = std::max(want, *cap * 3 / 2);
-  if (*p) {
-    if (pinned) (void)hipHostFree(*p);
-    else (void)hipFree(*p);
-    *p = nullptr;
-  }
-  hipError_t e = pinned ? hipHostMalloc(p, n) : hipMalloc(p, n);
-  if (e != hipSuccess) {
-    *cap = 0;
-    *p = nullptr;
-    return XCG_ENOMEM;
-  }
-  *cap = n;
-  return XCG_OK;
-}
-inline size_t ial(size_t v, size_t a) { return (v + a - 1) / a * a; }
+using xcg::align_up;
 int g_zi_par = 0;                    // 0: by batch size, 1: a wave per call, 2: a workgroup per call
 uint32_t g_zi_warm = xcg::zi::WARM_DEFAULT, g_zi_threads = 1024;   // region shape (A/B runs)
 // A workgroup per call up to this many calls: per call (1024 threads) it is
@@ -1477,20 +1462,19 @@ int xcg_zinflate_create(int device, uint32_t nstreams, xcg_zinflate** out) {
   xcg_zinflate* z = new xcg_zinflate();
   z->device = device;
   z->nstreams = nstreams;
-  if (hipMalloc(&z->st, sizeof(IState) * nstreams) != hipSuccess ||
-      hipMalloc(&z->hist, (size_t)WSIZE * nstreams) != hipSuccess ||
-      hipEventCreateWithFlags(&z->done, hipEventDisableTiming) != hipSuccess) {
-    delete z;
-    return XCG_ENOMEM;
-  }
+  auto fail = [&](int rc) {
+    xcg_zinflate_destroy(z);
+    return rc;
+  };
+  if (!(z->mem.dev(&z->st, sizeof(IState) * nstreams) && z->mem.dev(&z->hist, (size_t)WSIZE * nstreams)) ||
+      hipEventCreateWithFlags(&z->done, hipEventDisableTiming) != hipSuccess)
+    return fail(XCG_ENOMEM);
   std::vector<IState> init(nstreams);
   memset(init.data(), 0, sizeof(IState) * nstreams);
   for (auto& s : init) s.adler = 1;
   if (hipMemcpy(z->st, init.data(), sizeof(IState) * nstreams, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemset(z->hist, 0, (size_t)WSIZE * nstreams) != hipSuccess) {
-    delete z;
-    return XCG_EHIP;
-  }
+      hipMemset(z->hist, 0, (size_t)WSIZE * nstreams) != hipSuccess)
+    return fail(XCG_EHIP);
   *out = z;
   return XCG_OK;
 }
@@ -1499,14 +1483,8 @@ void xcg_zinflate_destroy(xcg_zinflate* z) {
   if (!z) return;
   (void)hipSetDevice(z->device);
   if (z->done) (void)hipEventSynchronize(z->done);
-  (void)hipFree(z->st);
-  (void)hipFree(z->hist);
-  (void)hipFree(z->scratch);
-  (void)hipFree(z->meta);
-  if (z->h_meta) (void)hipHostFree(z->h_meta);
+  z->mem.release_all();
   if (z->done) (void)hipEventDestroy(z->done);
-  if (z->hs_h) (void)hipHostFree(z->hs_h);
-  (void)hipFree(z->hs_d);
   if (z->hst) (void)hipStreamDestroy(z->hst);
   delete z;
 }
@@ -1532,7 +1510,7 @@ int xcg_zinflate_batch(xcg_zinflate* z, const uint8_t* d_in, const uint64_t* h_i
     c.stream = h_stream[i];
     c.out_cap = h_out_cap[i];
     c.i_off = io;
-    io += ial((size_t)PEND_CAP + c.len + IPAD, 256);
+    io += align_up((size_t)PEND_CAP + c.len + IPAD, 256);
     maxlen = std::max(maxlen, c.len);
   }
   // few calls: a workgroup per call (zi_inflate_kernel<16>) with RES_CAP
@@ -1541,12 +1519,14 @@ int xcg_zinflate_batch(xcg_zinflate* z, const uint8_t* d_in, const uint64_t* h_i
   // quarter workgroups (four calls per CU: one call's serial stretches overlap
   // the others') once the batch fills the CUs
   const bool quarter = g_zi_par == 3 || (g_zi_par == 0 && n > ZI_QUARTER_CALLS);
-  size_t o_I = 0, o_res = ial(io, 256), o_pres = ial(o_res + sizeof(IRes) * n, 256),
+  size_t o_I = 0, o_res = align_up(io, 256), o_pres = align_up(o_res + sizeof(IRes) * n, 256),
          o_end = par ? o_pres + 4ull * RES_CAP * n : o_pres;
   if (hipEventSynchronize(z->done) != hipSuccess) return XCG_EHIP;
-  if (igrow((void**)&z->scratch, &z->scratch_cap, o_end, false)) return XCG_ENOMEM;
-  size_t m_end = ial(sizeof(ICall) * n, 256);
-  if (igrow(&z->meta, &z->meta_cap, m_end, false) || igrow(&z->h_meta, &z->h_meta_cap, m_end, true)) return XCG_ENOMEM;
+  if (!z->mem.grow_bytes(&z->scratch, &z->scratch_cap, o_end, xcg::MEM_DEV)) return XCG_ENOMEM;
+  size_t m_end = align_up(sizeof(ICall) * n, 256);
+  if (!z->mem.grow_bytes(&z->meta, &z->meta_cap, m_end, xcg::MEM_DEV) ||
+      !z->mem.grow_bytes(&z->h_meta, &z->h_meta_cap, m_end, xcg::MEM_PINNED))
+    return XCG_ENOMEM;
   memcpy(z->h_meta, calls.data(), sizeof(ICall) * n);
   if (hipMemcpyAsync(z->meta, z->h_meta, m_end, hipMemcpyHostToDevice, st) != hipSuccess) return XCG_EHIP;
   IArgs a;
@@ -1601,12 +1581,13 @@ int xcg_zinflate_host(xcg_zinflate* z, const uint8_t* h_in, const uint64_t* h_in
   for (uint32_t i = 0; i < n; i++) {
     in_end = std::max(in_end, h_in_off[i] + h_len[i]);
     doff[i] = out_end;
-    out_end += ial(h_out_cap[i] ? h_out_cap[i] : 1, 4);
+    out_end += align_up(h_out_cap[i] ? h_out_cap[i] : 1, 4);
   }
   // staging: [len n][status n][in][out]
-  const size_t o_st = ial(4ull * n, 256), o_in = ial(o_st + 4ull * n, 256), o_out = ial(o_in + in_end + 1, 256),
-               o_end = ial(o_out + out_end, 256);
-  if (igrow((void**)&z->hs_h, &z->hs_hcap, o_end, true) || igrow((void**)&z->hs_d, &z->hs_dcap, o_end, false))
+  const size_t o_st = align_up(4ull * n, 256), o_in = align_up(o_st + 4ull * n, 256), o_out = align_up(o_in + in_end + 1, 256),
+               o_end = align_up(o_out + out_end, 256);
+  if (!z->mem.grow_bytes(&z->hs_h, &z->hs_hcap, o_end, xcg::MEM_PINNED) ||
+      !z->mem.grow_bytes(&z->hs_d, &z->hs_dcap, o_end, xcg::MEM_DEV))
     return XCG_ENOMEM;
   if (in_end) memcpy(z->hs_h + o_in, h_in, in_end);
   if (in_end && hipMemcpyAsync(z->hs_d + o_in, z->hs_h + o_in, in_end, hipMemcpyHostToDevice, z->hst) != hipSuccess)

@@ -519,26 +519,20 @@ bool lru_debug() {
   return on;
 }
 
-unsigned grid_for(uint64_t threads) { return (unsigned)((threads + 255) / 256); }
+using xcg::grid_for;
 
 // One multi-workgroup ordered scan over at most max_n elements.
 template <int K>
 int run_scan(XcgLruState* L, xcg::ScanArgs a, uint64_t max_n, hipStream_t st) {
   const uint32_t tiles = (uint32_t)((max_n + 1023) / 1024) + 1;
-  if (tiles > L->part_cap) {
-    (void)hipFree(L->part);
-    L->part = nullptr;
-    L->part_cap = 0;
-    if (hipMalloc(&L->part, 4ull * tiles * 2) != hipSuccess) return -5;
-    L->part_cap = tiles * 2;
-  }
+  if (!L->mem->grow(&L->part, &L->part_cap, tiles, tiles * 2, 4ull * tiles * 2, xcg::MEM_DEV)) return -5;
   a.part = L->part;
   hipLaunchKernelGGL(xcg::scan_count_kernel<K>, dim3(tiles), dim3(256), 0, st, a);
   hipLaunchKernelGGL(xcg::scan_emit_kernel<K>, dim3(tiles), dim3(256), 0, st, a);
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
-xcg::ScanArgs scan_args(XcgLruState* L, uint32_t* nseg) {
+xcg::ScanArgs scan_args(XcgLruState* L, const LruBatch& b, uint32_t* nseg) {
   xcg::ScanArgs a{};
   a.tot = L->tot;
   a.queue = L->queue;
@@ -549,8 +543,8 @@ xcg::ScanArgs scan_args(XcgLruState* L, uint32_t* nseg) {
   a.alive = L->alive;
   a.lastref = L->lastref;
   a.clock = L->clock;
-  a.evslot = L->evslot;
-  a.evtime = L->evtime;
+  a.evslot = b.evslot;
+  a.evtime = b.evtime;
   a.queue2 = L->queue2;
   a.nseg = nseg;
   a.C = L->C;
@@ -564,6 +558,7 @@ LruBatch batch_of(const XcgStreamArgs& a) {
   b.decl = a.decl; b.ndecl = a.ndecl; b.maxd = a.maxd;
   b.ev = a.ev; b.nev = a.nev; b.maxe = a.maxe;
   b.need = a.need; b.bad_t = a.bad_t; b.bad_hi = a.bad_hi;
+  b.evslot = a.ev_slot; b.evtime = a.ev_time; b.ev_base = a.ev_base; b.enter_base = a.enter_base;
   b.g = a.g;
   b.status = a.status;
   b.ev_bound = (uint64_t)a.n * a.maxe;
@@ -580,15 +575,15 @@ int lru_times(const LruBatch& b, XcgLruState* L, bool check, hipStream_t st, boo
   using namespace xcg;
   const uint32_t n = b.n;
   hipLaunchKernelGGL(lru_prep_kernel, dim3(1), dim3(1024), 0, st, n, b.nev, b.ndecl, b.maxe, L->C,
-                     (const uint32_t*)b.g.nseg, L->ev_base, L->enter_base, b.need, L->tot, skip);
+                     (const uint32_t*)b.g.nseg, b.ev_base, b.enter_base, b.need, L->tot, skip);
   const unsigned cg = grid_for(L->C) < 1024 ? grid_for(L->C) : 1024;
   hipLaunchKernelGGL(lru_fill64x4_kernel, dim3(cg), dim3(256), 0, st, Fill64{L->hmin, L->C, NEVER},
                      Fill64{L->tau, L->C, NEVER}, Fill64{nullptr, 0u, 0ull}, Fill64{nullptr, 0u, 0ull}, skip);
-  const EvRows R{(const uint4*)b.ev, b.nev, (const uint32_t*)L->ev_base, b.maxe, b.dense != 0};
+  const EvRows R{(const uint4*)b.ev, b.nev, (const uint32_t*)b.ev_base, b.maxe, b.dense != 0};
   const dim3 wgrid((n + 3) / 4);
-  hipLaunchKernelGGL(lru_events_kernel, wgrid, dim3(256), 0, st, n, R, (const uint32_t*)L->enter_base,
+  hipLaunchKernelGGL(lru_events_kernel, wgrid, dim3(256), 0, st, n, R, (const uint32_t*)b.enter_base,
                      (const uint32_t*)L->tot, L->C, L->hmin, L->tau, skip);
-  ScanArgs ra = scan_args(L, nullptr);
+  ScanArgs ra = scan_args(L, b, nullptr);
   ra.gate = skip;
   if (run_scan<SK_RANK>(L, ra, L->C, st)) return -5;
   if (check)
@@ -622,6 +617,7 @@ int lru_seed_guess(const XcgStreamArgs& a, XcgLruState* L, hipStream_t st) {
   const uint32_t n = a.n;
   const unsigned cg = grid_for(L->C) < 1024 ? grid_for(L->C) : 1024;
   const HashTab g = tab_of(a.g), b{a.b_keys, a.b_vals, a.b_mask};   // (b: the rounds rebuild it)
+  const LruBatch lb = batch_of(a);
   (void)cg;
   hipLaunchKernelGGL(lru_fill64x4_kernel, dim3(1024), dim3(256), 0, st, Fill64{b.keys, b.mask + 1, EMPTY_KEY},
                      Fill64{b.vals, b.mask + 1, ~0ull}, Fill64{L->hmin, L->C, NEVER}, Fill64{L->tau, L->C, NEVER},
@@ -639,15 +635,15 @@ int lru_seed_guess(const XcgStreamArgs& a, XcgLruState* L, hipStream_t st) {
   for (int it = 0; it < iters; ++it) {
     const uint64_t* pt = it ? (const uint64_t*)L->ptime : nullptr;
     hipLaunchKernelGGL(lru_seed_classify_kernel, wgrid, dim3(256), 0, st, n, (const uint4*)a.decl,
-                       (const uint32_t*)a.ndecl, a.maxd, a.chunk_len, g, b, cnt, (const uint32_t*)L->enter_base,
+                       (const uint32_t*)a.ndecl, a.maxd, a.chunk_len, g, b, cnt, (const uint32_t*)a.enter_base,
                        (const uint32_t*)L->tot, L->C, L->hmin, L->tau, 0, pt);
     hipLaunchKernelGGL(lru_prep_kernel, dim3(1), dim3(1024), 0, st, n, (const uint32_t*)a.nev, (const uint32_t*)cnt,
-                       a.maxe, L->C, (const uint32_t*)a.g.nseg, L->ev_base, L->enter_base, a.need, L->tot,
+                       a.maxe, L->C, (const uint32_t*)a.g.nseg, a.ev_base, a.enter_base, a.need, L->tot,
                        (const uint32_t*)nullptr);
     hipLaunchKernelGGL(lru_seed_classify_kernel, wgrid, dim3(256), 0, st, n, (const uint4*)a.decl,
-                       (const uint32_t*)a.ndecl, a.maxd, a.chunk_len, g, b, cnt, (const uint32_t*)L->enter_base,
+                       (const uint32_t*)a.ndecl, a.maxd, a.chunk_len, g, b, cnt, (const uint32_t*)a.enter_base,
                        (const uint32_t*)L->tot, L->C, L->hmin, L->tau, 1, pt);
-    ScanArgs sa = scan_args(L, nullptr);
+    ScanArgs sa = scan_args(L, lb, nullptr);
     if (it + 1 < iters) sa.hmin_reset = L->hmin;
     if (run_scan<SK_RANK>(L, sa, L->C, st)) return -5;
   }
@@ -670,7 +666,7 @@ int lru_commit_dev(const LruBatch* bp, XcgLruState* L, const uint32_t* gate, hip
   hipLaunchKernelGGL(lru_unmark_kernel, dim3(cg), dim3(256), 0, st, L->alive, C, gate);
   hipLaunchKernelGGL(lru_mark_kernel, dim3(grid_for(C)), dim3(256), 0, st, (const uint32_t*)L->tot,
                      (const uint32_t*)L->queue, (const uint64_t*)L->hmin, (const uint64_t*)L->wpop, L->alive, gate);
-  ScanArgs fa = scan_args(L, nullptr);
+  ScanArgs fa = scan_args(L, b, nullptr);
   fa.gate = gate;
   if (run_scan<SK_FREE>(L, fa, C, st)) return -5;
   const HashTab g = tab_of(b.g);
@@ -681,13 +677,13 @@ int lru_commit_dev(const LruBatch* bp, XcgLruState* L, const uint32_t* gate, hip
                      (const uint64_t*)L->skey, g, fs, b.status, gate);
   const uint64_t waves = (uint64_t)n * b.maxd;
   hipLaunchKernelGGL(lru_insert_new_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, n,
-                     (const uint4*)b.decl, b.ndecl, b.maxd, (const uint32_t*)L->enter_base,
+                     (const uint4*)b.decl, b.ndecl, b.maxd, (const uint32_t*)b.enter_base,
                      (const uint32_t*)L->freel, b.in, b.chunk_off, L->skey, L->alive, g, b.g.pool, fs, b.status, gate);
-  const EvRows R{(const uint4*)b.ev, b.nev, (const uint32_t*)L->ev_base, b.maxe, b.dense != 0};
-  hipLaunchKernelGGL(lru_lastref_kernel, dim3((n + 3) / 4), dim3(256), 0, st, n, R, (const uint32_t*)L->enter_base,
-                     (const uint32_t*)L->freel, g, L->clock, L->lastref, L->evslot, L->evtime, gate);
+  const EvRows R{(const uint4*)b.ev, b.nev, (const uint32_t*)b.ev_base, b.maxe, b.dense != 0};
+  hipLaunchKernelGGL(lru_lastref_kernel, dim3((n + 3) / 4), dim3(256), 0, st, n, R, (const uint32_t*)b.enter_base,
+                     (const uint32_t*)L->freel, g, L->clock, L->lastref, b.evslot, b.evtime, gate);
   {
-    ScanArgs qa = scan_args(L, b.g.nseg);
+    ScanArgs qa = scan_args(L, b, b.g.nseg);
     qa.gate = gate;
     if (run_scan<SK_QUEUE>(L, qa, (uint64_t)C + b.ev_bound, st)) return -5;
   }

@@ -1133,6 +1133,7 @@ struct XcgPairState;
 
 // One XCodecDisk: the ring's blocks (device arrays) and the fronts on it.
 struct XcgDiskState {
+  xcg::DevMem mem;                 // the ring's device arrays
   uint64_t nb = 0;                 // index blocks
   uint32_t D = 0;                  // nb * 204 data blocks
   uint64_t dclock = 0;             // entries written to the disk (every front)
@@ -1170,6 +1171,7 @@ struct XcgDiskState {
 };
 
 struct XcgPairState {
+  xcg::DevMem mem;                 // the front's arrays, the pass scratch, a pool without virtual memory
   uint32_t C = 0;                  // primary limit in segments
   // XCodecCachePair over an unbounded XCodecMemoryCache (limit 0: enter never
   // evicts, xcodec_cache.h:303-318): C is then only the primary's capacity,
@@ -1256,8 +1258,6 @@ bool pair_debug() {
   return on;
 }
 
-unsigned grid_for(uint64_t threads) { return (unsigned)((threads + 255) / 256); }
-
 // Guesses of a sub-batch's tiling seed replayed before its first parse
 // (read per sub-batch).  Default 1: on C5-PAIR-LAPS three guesses save two of
 // fifteen parse passes but each costs a replay with departures (~1.2 ms per
@@ -1268,61 +1268,42 @@ int pair_seed_iters() {
   return k < 1 ? 1 : (k > 8 ? 8 : k);
 }
 
-template <class T>
-bool grow(T** p, uint64_t* cap, uint64_t want) {
-  if (*cap >= want) return true;
-  (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  if (hipMalloc(p, want * sizeof(T)) != hipSuccess) return false;
-  *cap = want;
-  return true;
-}
-
 // Pass scratch for np positions, n chunks, etot entities.
 int ensure_scratch(XcgPairState* P, uint64_t np, uint64_t n, uint64_t etot) {
+  DevMem& m = P->mem;
+  struct Arr { void** p; size_t sz; };             // a field and its bytes per element
+#define ARR(f) {(void**)&P->f, sizeof(*P->f)}
   if (np + 1 > P->np_cap) {
     const uint64_t cap = std::max<uint64_t>(np + 1, P->np_cap + P->np_cap / 2);
-    void** arrs[] = {(void**)&P->ent, (void**)&P->yent, (void**)&P->kind, (void**)&P->tim, (void**)&P->hsh,
-                     (void**)&P->skey, (void**)&P->sval, (void**)&P->sk, (void**)&P->sv, (void**)&P->prv,
-                     (void**)&P->nxt, (void**)&P->isr, (void**)&P->rc, (void**)&P->phit, (void**)&P->app,
-                     (void**)&P->clk, (void**)&P->slow, (void**)&P->f1, (void**)&P->f2, (void**)&P->r1,
-                     (void**)&P->r2, (void**)&P->missrow, (void**)&P->moves, (void**)&P->tflag,
-                     (void**)&P->ddeath, (void**)&P->sa, (void**)&P->sb, (void**)&P->nq, (void**)&P->tnew};
-    const size_t sz[] = {4, 4, 1, 8, 8, 4, 4, 4, 4, 4, 4, 4, 4, 1, 4, 4, 4, 4, 4, 4, 4, 4, 32, 1, 8, 8, 8, 4, 1};
-    for (size_t k = 0; k < sizeof(sz) / sizeof(sz[0]); ++k) {
-      (void)hipFree(*arrs[k]);
-      *arrs[k] = nullptr;
-    }
+    const Arr arrs[] = {ARR(ent), ARR(yent), ARR(kind), ARR(tim), ARR(hsh), ARR(skey), ARR(sval), ARR(sk),
+                        ARR(sv), ARR(prv), ARR(nxt), ARR(isr), ARR(rc), ARR(phit), ARR(app), ARR(clk),
+                        ARR(slow), ARR(f1), ARR(f2), ARR(r1), ARR(r2), ARR(missrow),
+                        {(void**)&P->moves, 32},   // (two uint4 per position)
+                        ARR(tflag), ARR(ddeath), ARR(sa), ARR(sb), ARR(nq), ARR(tnew)};
+    for (const Arr& a : arrs) m.release(*a.p), *a.p = nullptr;
     P->np_cap = 0;
-    for (size_t k = 0; k < sizeof(sz) / sizeof(sz[0]); ++k)
-      if (hipMalloc(arrs[k], (cap + 1) * sz[k]) != hipSuccess) return -5;
+    for (const Arr& a : arrs)
+      if (!m.dev(a.p, (cap + 1) * a.sz)) return -5;
     P->np_cap = cap;
   }
   if (n + 1 > P->n_cap) {
-    (void)hipFree(P->pbase);
-    (void)hipFree(P->pcnt);
+    m.release(P->pbase);
+    m.release(P->pcnt);
     P->pbase = P->pcnt = nullptr;
     P->n_cap = 0;
-    if (hipMalloc(&P->pbase, 4 * (n + 1)) != hipSuccess || hipMalloc(&P->pcnt, 4 * (n + 1)) != hipSuccess) return -5;
+    if (!(m.dev(&P->pbase, 4 * (n + 1)) && m.dev(&P->pcnt, 4 * (n + 1)))) return -5;
     P->n_cap = n + 1;
   }
-  uint64_t ec = P->et_cap, lc = P->el_cap;
-  if (!grow(&P->erun, &ec, etot) || !grow(&P->elast, &lc, etot)) return -5;
-  P->et_cap = ec;
-  P->el_cap = lc;
+  if (!m.grow_exact(&P->erun, &P->et_cap, etot) || !m.grow_exact(&P->elast, &P->el_cap, etot)) return -5;
   if (etot > P->ex_cap) {
-    void** arrs[] = {(void**)&P->erend, (void**)&P->einit, (void**)&P->ecov, (void**)&P->egap, (void**)&P->etail};
-    const size_t sz[] = {4, 8, 4, 4, 4};
+    const Arr arrs[] = {ARR(erend), ARR(einit), ARR(ecov), ARR(egap), ARR(etail)};
     P->ex_cap = 0;
-    for (size_t k = 0; k < 5; ++k) {
-      (void)hipFree(*arrs[k]);
-      *arrs[k] = nullptr;
-    }
-    for (size_t k = 0; k < 5; ++k)
-      if (hipMalloc(arrs[k], etot * sz[k] + 8) != hipSuccess) return -5;
+    for (const Arr& a : arrs) m.release(*a.p), *a.p = nullptr;
+    for (const Arr& a : arrs)
+      if (!m.dev(a.p, etot * a.sz + 8)) return -5;
     P->ex_cap = etot;
   }
+#undef ARR
   // rocprim temporary storage for the largest sort / scan of this size
   size_t a = 0, b = 0, c = 0;
   (void)rocprim::radix_sort_pairs<PairSortCfg>(nullptr, a, P->skey, P->sk, P->sval, P->sv, (uint32_t)np, 0, 32);
@@ -1336,14 +1317,7 @@ int ensure_scratch(XcgPairState* P, uint64_t np, uint64_t n, uint64_t etot) {
   (void)rocprim::inclusive_scan(nullptr, e2, P->sa, P->sb, (size_t)np + 1, rocprim::maximum<uint64_t>());
   (void)rocprim::inclusive_scan(nullptr, e3, P->sa, P->sb, (size_t)np + 1, rocprim::minimum<uint64_t>());
   const uint64_t want = std::max(std::max(std::max(a, b), c), std::max(std::max(e1, e2), e3)) + 256;
-  if (want > P->tmp_cap) {
-    (void)hipFree(P->tmp);
-    P->tmp = nullptr;
-    P->tmp_cap = 0;
-    if (hipMalloc(&P->tmp, want) != hipSuccess) return -5;
-    P->tmp_cap = want;
-  }
-  return 0;
+  return m.grow(&P->tmp, &P->tmp_cap, want, want, want, MEM_DEV) ? 0 : -5;
 }
 
 int scan_u32(XcgPairState* P, const uint32_t* in, uint32_t* out, uint64_t n, hipStream_t st) {
@@ -1412,8 +1386,8 @@ int replay(XcgPairState* P, const RowSrc& rs, const HashTab& g, bool want_leave,
   if (etot64 >= (1ull << 31)) return -95;
   const uint32_t etot = (uint32_t)etot64;
   if (!P->cnt) {
-    if (hipMalloc(&P->cnt, sizeof(PairCnt)) != hipSuccess || hipHostMalloc(&P->h_cnt, sizeof(PairCnt)) != hipSuccess ||
-        hipHostMalloc(&P->h_small, 256) != hipSuccess)
+    if (!(P->mem.dev(&P->cnt, sizeof(PairCnt)) && P->mem.pinned(&P->h_cnt, sizeof(PairCnt)) &&
+          P->mem.pinned(&P->h_small, 256)))
       return -5;
   }
   if (hipMemsetAsync(P->cnt, 0, sizeof(PairCnt), st) != hipSuccess) return -5;
@@ -1456,7 +1430,7 @@ int replay(XcgPairState* P, const RowSrc& rs, const HashTab& g, bool want_leave,
   if (!rs.dec) {
     const uint64_t want = std::max<uint64_t>(1024, 2ull << (64 - __builtin_clzll(R + 1)));
     uint64_t kc = P->bm_cap, vc = P->bm_cap;
-    if (!grow(&P->bm_keys, &kc, want) || !grow(&P->bm_vals, &vc, want)) return -5;
+    if (!P->mem.grow_exact(&P->bm_keys, &kc, want) || !P->mem.grow_exact(&P->bm_vals, &vc, want)) return -5;
     P->bm_cap = std::min(kc, vc);
     d.bm = HashTab{P->bm_keys, P->bm_vals, (uint32_t)(want - 1)};
     hipLaunchKernelGGL(pr_fill64_kernel, dim3(grid_for(want)), dim3(256), 0, st, P->bm_keys, want, EMPTY_KEY);
@@ -1469,7 +1443,8 @@ int replay(XcgPairState* P, const RowSrc& rs, const HashTab& g, bool want_leave,
   if (n) hipLaunchKernelGGL(pr_rows_kernel, dim3((n + 3) / 4), dim3(256), 0, st, d);
   if (rs.dec && R) {                               // decode HITs: latest definer of the hash
     uint64_t c1 = P->hk_cap, c2 = P->hk_cap, c3 = P->hk_cap, c4 = P->hk_cap;
-    if (!grow(&P->hk, &c1, R) || !grow(&P->hk2, &c2, R) || !grow(&P->hv, &c3, R) || !grow(&P->hv2, &c4, R))
+    if (!P->mem.grow_exact(&P->hk, &c1, R) || !P->mem.grow_exact(&P->hk2, &c2, R) ||
+        !P->mem.grow_exact(&P->hv, &c3, R) || !P->mem.grow_exact(&P->hv2, &c4, R))
       return -5;
     P->hk_cap = std::min(std::min(c1, c2), std::min(c3, c4));
     if (hipMemcpyAsync(P->hk, P->hsh + P->pcount, 8 * R, hipMemcpyDeviceToDevice, st) != hipSuccess) return -5;
@@ -1514,9 +1489,7 @@ int replay(XcgPairState* P, const RowSrc& rs, const HashTab& g, bool want_leave,
     const uint32_t nbk = (uint32_t)((np + (1ull << bsh) - 1) >> bsh);
     const uint64_t w = (uint64_t)nbk + 1;
     const uint64_t cells = (uint64_t)nbk * w + TSEG * w;
-    uint64_t tc = P->tab_cap;
-    if (!grow(&P->tab, &tc, cells)) return -5;
-    P->tab_cap = tc;
+    if (!P->mem.grow_exact(&P->tab, &P->tab_cap, cells)) return -5;
     d.tab = P->tab;
     d.bsh = bsh;
     d.nbk = nbk;
@@ -1582,10 +1555,10 @@ int replay(XcgPairState* P, const RowSrc& rs, const HashTab& g, bool want_leave,
 // The primary's arrays must outlive one replay; the commit's slot arrays too.
 int ensure_front_arrays(XcgPairState* P) {
   if (P->occ) return 0;
-  if (hipMalloc(&P->occ, 4ull * P->C) != hipSuccess || hipMalloc(&P->freel, 4ull * P->C) != hipSuccess ||
-      hipMalloc(&P->ofl, 4ull * (P->C + 1)) != hipSuccess || hipMalloc(&P->ofr, 4ull * (P->C + 1)) != hipSuccess)
-    return -5;
-  return 0;
+  DevMem& m = P->mem;
+  return m.dev(&P->occ, 4ull * P->C) && m.dev(&P->freel, 4ull * P->C) && m.dev(&P->ofl, 4ull * (P->C + 1)) &&
+                 m.dev(&P->ofr, 4ull * (P->C + 1))
+             ? 0 : -5;
 }
 
 // G from the state: wipe, then every primary slot and live own disk block.
@@ -1643,9 +1616,7 @@ int pair_commit(XcgPairState* P, const PairGpu& G, hipStream_t st) {
     return -5;
   const uint32_t pc = P->h_small[0], nmove = P->h_cnt->nmove, nstage = P->h_cnt->nstage;
   if (pc > P->C) return -5;
-  uint64_t sc = P->stg_cap;
-  if (!grow(&P->staging, &sc, (uint64_t)std::max<uint32_t>(nstage, 1) * SEG)) return -5;
-  P->stg_cap = sc;
+  if (!P->mem.grow_exact(&P->staging, &P->stg_cap, (uint64_t)std::max<uint32_t>(nstage, 1) * SEG)) return -5;
   if (nmove) {
     hipLaunchKernelGGL(pair_stage_kernel, dim3((nmove + 3) / 4), dim3(256), 0, st, (const uint4*)P->moves,
                        (const PairCnt*)P->cnt, (const uint8_t*)G.g.pool, P->staging);
@@ -1695,10 +1666,10 @@ PairGpu gpu_of(const XcgStreamArgs& a) {
 int disk_bind(XcgDiskState* K, int device) {
   if (K->device >= 0) return K->device == device ? 0 : -22;
   const uint64_t D = K->D;
-  if (hipMalloc(&K->dkey, 8 * D) != hipSuccess || hipMalloc(&K->dent, 8 * D) != hipSuccess ||
-      hipMalloc(&K->dxuid, 4 * D) != hipSuccess || hipMemset(K->dkey, 0xFF, 8 * D) != hipSuccess ||
+  if (!(K->mem.dev(&K->dkey, 8 * D) && K->mem.dev(&K->dent, 8 * D) && K->mem.dev(&K->dxuid, 4 * D)) ||
+      hipMemset(K->dkey, 0xFF, 8 * D) != hipSuccess ||
       hipMemset(K->dent, 0xFF, 8 * D) != hipSuccess || hipMemset(K->dxuid, 0xFF, 4 * D) != hipSuccess) {
-    (void)hipFree(K->dkey); (void)hipFree(K->dent); (void)hipFree(K->dxuid);
+    K->mem.release_all();
     K->dkey = K->dent = nullptr;
     K->dxuid = nullptr;
     return -12;
@@ -1706,8 +1677,6 @@ int disk_bind(XcgDiskState* K, int device) {
   K->device = device;
   return 0;
 }
-
-size_t round_up(size_t v, size_t g) { return (v + g - 1) / g * g; }
 
 // The front's pool: C primary segments followed by the disk's D blocks at
 // pool + (C + i) * 2048.  HIP virtual memory maps the disk's one physical
@@ -1728,7 +1697,7 @@ int map_pool(XcgPairState* P, int device) {
       // device already holds (keep 4 GiB free) or the caller asks for the host
       // tier -- then pinned host memory behind the same addresses, which the
       // kernels read and write over PCIe (a spill level below HBM).
-      const size_t sd = round_up((size_t)K->D * SEG + 256, gran);
+      const size_t sd = align_up((size_t)K->D * SEG + 256, gran);
       size_t fr = 0, tot = 0;
       const bool fits = hipMemGetInfo(&fr, &tot) == hipSuccess && fr > sd + (4ull << 30);
       const bool want_host = (K->flags & 1u) != 0 || (!(K->flags & 2u) && !fits);
@@ -1786,7 +1755,7 @@ int map_pool(XcgPairState* P, int device) {
         (void)hipGetLastError();
       }
     }
-    const size_t sp = round_up((size_t)P->C * SEG, gran ? gran : 1);
+    const size_t sp = align_up((size_t)P->C * SEG, gran ? gran : 1);
     bool prim = false, reserved = false, m1 = false, m2 = false;
     if (ok) prim = ok = hipMemCreate(&P->prim_h, sp, &prop, 0) == hipSuccess;
     if (ok) reserved = ok = hipMemAddressReserve(&P->va, sp + K->pool_bytes, 0, nullptr, 0) == hipSuccess;
@@ -1815,7 +1784,7 @@ int map_pool(XcgPairState* P, int device) {
     P->va = nullptr;
     (void)hipGetLastError();
   }
-  if (hipMalloc(&P->pool, ((uint64_t)P->C + P->D) * SEG + 256) != hipSuccess) return -12;
+  if (!P->mem.dev(&P->pool, ((uint64_t)P->C + P->D) * SEG + 256)) return -12;
   P->pool_vmm = false;
   return 0;
 }
@@ -1828,33 +1797,9 @@ void unmap_pool(XcgPairState* P) {
     (void)hipMemAddressFree(P->va, P->va_bytes);
     (void)hipMemRelease(P->prim_h);
   } else {
-    (void)hipFree(P->pool);
+    P->mem.release(P->pool);
   }
   P->pool = nullptr;
-}
-
-void free_scratch(XcgPairState* P) {
-  void* arrs[] = {P->ent, P->yent, P->kind, P->tim, P->hsh, P->skey, P->sval, P->sk, P->sv, P->prv, P->nxt,
-                  P->isr, P->rc, P->phit, P->app, P->clk, P->slow, P->f1, P->f2, P->r1, P->r2, P->missrow,
-                  P->moves, P->pbase, P->pcnt, P->elast, P->tflag, P->ddeath, P->erep, P->erun, P->erend, P->einit, P->ecov, P->egap, P->etail, P->sa, P->sb, P->nq, P->tnew, P->tab, P->occ, P->freel, P->ofl, P->ofr, P->hk, P->hk2,
-                  P->hv, P->hv2, P->bm_keys, P->bm_vals, P->staging, P->tmp, P->cnt};
-  for (void* p : arrs) (void)hipFree(p);
-  if (P->h_small) (void)hipHostFree(P->h_small);
-  if (P->h_cnt) (void)hipHostFree(P->h_cnt);
-}
-
-// XCodecHash::hash of one segment (xcodec/xcodec_hash.h:166-174), host side:
-// the reload's check of an index entry against its data block.
-uint64_t host_hash(const uint8_t* w) {
-  uint32_t s1 = 0, s2 = 0, b1 = 0, b2 = 0;
-  for (int k = 0; k < SEG; ++k) {
-    s1 += (uint32_t)w[k] + 1u;
-    s2 += s1;
-    b1 += w[k] ? (uint32_t)__builtin_ctz(w[k]) + 1u : 0u;
-    b2 += b1;
-  }
-  const uint32_t bits = (b1 << 16) + b2, bytes = (s1 << 20) + s2;
-  return ((uint64_t)bits << 36) + (uint64_t)bytes;
 }
 
 constexpr uint32_t REG_BLOCKS = 18, REG_ENTRIES = 2048 / 36, CHECK_BOUNDARY = 80, XUIDS = 1024;
@@ -2027,7 +1972,7 @@ int load_volume(XcgDiskState* K, int fd) {
       const uint32_t xu = K->h_xuid[slot];
       if (h == NOKEY || xu >= XUIDS || K->uuid[xu].empty()) continue;
       index[xu].erase(h);                                   // ("Replacing previous cache entry.")
-      if (check && host_hash(&K->h_data[slot * SEG]) != h) {
+      if (check && host_seg_hash(&K->h_data[slot * SEG]) != h) {
         if (cib > b) {                                      // rewrite the block with errors
           invalidate(b);
           cib = b;
@@ -2079,7 +2024,7 @@ int xcg_disk_state_create(uint64_t disk_bytes, uint32_t flags, XcgDiskState** ou
 
 void xcg_disk_state_release(XcgDiskState* K) {
   if (!K || --K->refs > 0) return;
-  (void)hipFree(K->dkey); (void)hipFree(K->dent); (void)hipFree(K->dxuid);
+  K->mem.release_all();
   if (K->dva) {
     (void)hipDeviceSynchronize();
     (void)hipMemUnmap(K->dva, K->pool_bytes);
@@ -2093,14 +2038,14 @@ void xcg_disk_state_stats(const XcgDiskState* K, uint64_t* st) {
   uint64_t live = 0, fronts = 0;
   for (const XcgPairState* f : K->fronts) fronts += f != nullptr;
   if (K->device >= 0) {
+    DevMem mem;                    // (the probe word, freed on return)
     uint32_t* d = nullptr;
     uint32_t h = 0;
-    if (hipMalloc(&d, 4) == hipSuccess && hipMemset(d, 0, 4) == hipSuccess) {
+    if (mem.dev(&d, 4) && hipMemset(d, 0, 4) == hipSuccess) {
       hipLaunchKernelGGL(pair_count_live_kernel, dim3(grid_for(K->D)), dim3(256), 0, nullptr,
                          (const uint64_t*)K->dent, (const uint32_t*)K->dxuid, K->D, (uint32_t)K->nb, K->dclock, NIL, d);
       if (hipMemcpy(&h, d, 4, hipMemcpyDeviceToHost) == hipSuccess) live = h;
     }
-    (void)hipFree(d);
   }
   st[0] = live;
   st[1] = K->dclock;
@@ -2162,16 +2107,13 @@ int xcg_pair_state_create(uint32_t C, XcgDiskState* K, const char* uuid36, int w
   const uint64_t ids = (uint64_t)C + P->D;
   auto fail = [&](int rc) {
     unmap_pool(P);
-    (void)hipFree(P->pkey); (void)hipFree(P->pdisk); (void)hipFree(P->lru); (void)hipFree(P->lru2);
-    (void)hipFree(P->ptime);
-    free_scratch(P);
+    P->mem.release_all();
     delete P;
     return rc;
   };
-  if (hipMalloc(&P->pkey, 8ull * C) != hipSuccess || hipMalloc(&P->pdisk, 8ull * C) != hipSuccess ||
-      hipMalloc(&P->lru, 4ull * C) != hipSuccess || hipMalloc(&P->lru2, 4ull * C) != hipSuccess ||
-      hipMalloc(&P->ptime, 8 * ids) != hipSuccess ||
-      hipMalloc(&P->erep, 4 * ids) != hipSuccess ||
+  DevMem& m = P->mem;
+  if (!(m.dev(&P->pkey, 8ull * C) && m.dev(&P->pdisk, 8ull * C) && m.dev(&P->lru, 4ull * C) &&
+        m.dev(&P->lru2, 4ull * C) && m.dev(&P->ptime, 8 * ids) && m.dev(&P->erep, 4 * ids)) ||
       hipMemset(P->pkey, 0xFF, 8ull * C) != hipSuccess || hipMemset(P->pdisk, 0xFF, 8ull * C) != hipSuccess ||
       hipMemset(P->ptime, 0xFF, 8 * ids) != hipSuccess || ensure_front_arrays(P) != 0 || map_pool(P, device) != 0)
     return fail(-12);
@@ -2374,9 +2316,7 @@ void xcg_pair_state_destroy(XcgPairState* P) {
                        (const uint32_t*)K->dxuid, K->D, (uint32_t)P->xuid);
   (void)hipDeviceSynchronize();
   unmap_pool(P);
-  (void)hipFree(P->pkey); (void)hipFree(P->pdisk); (void)hipFree(P->lru); (void)hipFree(P->lru2);
-  (void)hipFree(P->ptime);
-  free_scratch(P);
+  P->mem.release_all();
   if (K) {
     K->fronts[P->xuid] = nullptr;
     xcg_disk_state_release(K);
@@ -2408,14 +2348,14 @@ int xcg_pair_state_clear(XcgPairState* P) {
 
 void xcg_pair_state_stats(const XcgPairState* P, uint64_t* st) {
   const XcgDiskState* K = P->disk;
+  DevMem mem;                      // (the probe word, freed on return)
   uint32_t h = 0;
   uint32_t* d = nullptr;
-  if (hipMalloc(&d, 4) == hipSuccess && hipMemset(d, 0, 4) == hipSuccess) {
+  if (mem.dev(&d, 4) && hipMemset(d, 0, 4) == hipSuccess) {
     hipLaunchKernelGGL(pair_count_live_kernel, dim3(grid_for(K->D)), dim3(256), 0, nullptr, (const uint64_t*)K->dent,
                        (const uint32_t*)K->dxuid, K->D, (uint32_t)K->nb, K->dclock, (uint32_t)P->xuid, d);
     (void)hipMemcpy(&h, d, 4, hipMemcpyDeviceToHost);
   }
-  (void)hipFree(d);
   st[0] = P->pcount;
   st[1] = h;
   st[2] = K->dclock;
@@ -2499,21 +2439,19 @@ int xcg_pair_encode_stream(const XcgStreamArgs* a0, XcgPairState* P, int* rounds
              (!a.bad_t || (hipMemsetAsync(a.bad_t, 0xFF, 4ull * m, st) == hipSuccess &&
                            hipMemsetAsync(a.bad_hi, 0, 4ull * m, st) == hipSuccess));
     };
+    StreamTemp flags_tmp(st);                        // (freed on `st` when the sub-batch is done, or fails)
     uint32_t* scratch_flags = nullptr;
     if (!a.bad_t) {                                  // (no restart arrays: flags into scratch)
-      if (hipMallocAsync((void**)&scratch_flags, 8ull * m, st) != hipSuccess) return -5;
+      if (!flags_tmp.alloc(&scratch_flags, 8ull * m)) return -5;
       rs.bad_t = scratch_flags;
       rs.bad_hi = scratch_flags + m;
     }
-    auto done_scratch = [&]() {
-      if (scratch_flags) (void)hipFreeAsync(scratch_flags, st);
-    };
     // The rounds start from each chunk's tiling (its cold parse).  ptime is
     // NEVER (no cached entry leaves) unless the last sub-batch needed more than
     // one pass: then the first guess is the tiling seed's own references,
     // replayed (a cached tile is a lookup hit, a repeat of an earlier tile a hit
     // on its declaration, every other tile a declaration).
-    if (xcg_launch_seed_tiling(&a, st)) { done_scratch(); return -5; }
+    if (xcg_launch_seed_tiling(&a, st)) return -5;
     const clk::time_point t1 = clk::now();
     if (P->prev_passes > 1) {
       const HashTab b{a.b_keys, a.b_vals, a.b_mask};
@@ -2529,10 +2467,10 @@ int xcg_pair_encode_stream(const XcgStreamArgs* a0, XcgPairState* P, int* rounds
         hipLaunchKernelGGL(pair_seed_events_kernel, dim3((m + 3) / 4), dim3(256), 0, st, m, (const uint4*)a.decl,
                            (const uint32_t*)a.ndecl, a.maxd, a.chunk_len, g, b, (uint4*)a.ev, a.nev, a.maxe,
                            it ? (const uint64_t*)P->ptime : nullptr);
-        if (!clear_flags()) { done_scratch(); return -5; }
+        if (!clear_flags()) return -5;
         PassOut o;
         const int rc = replay(P, rs, g, true, &o, st);
-        if (rc) { done_scratch(); return rc; }
+        if (rc) return rc;
         if (o.split) break;                        // (a guess the replay declines: keep the last times)
       }
     }
@@ -2548,14 +2486,14 @@ int xcg_pair_encode_stream(const XcgStreamArgs* a0, XcgPairState* P, int* rounds
       const clk::time_point q0 = clk::now();
       const int rc = xcg_launch_encode_stream(&a, &r, st);
       rounds += r;
-      if (rc) { done_scratch(); return rc; }
+      if (rc) return rc;
       if (pair_debug()) (void)hipStreamSynchronize(st);
       const clk::time_point q1 = clk::now();
-      if (!clear_flags()) { done_scratch(); return -5; }
+      if (!clear_flags()) return -5;
       PassOut o;
       const int prc = replay(P, rs, g, false, &o, st);
       if (prc == -75) { split = true; break; }
-      if (prc) { done_scratch(); return prc; }
+      if (prc) return prc;
       const clk::time_point q2 = clk::now();
       t_parse += ms(q0, q1);
       t_replay += ms(q1, q2);
@@ -2567,7 +2505,6 @@ int xcg_pair_encode_stream(const XcgStreamArgs* a0, XcgPairState* P, int* rounds
       // else: the replay flagged the chunks (need / bad_t / bad_hi) and set ptime
     }
     if (!done) {
-      done_scratch();
       if (m == 1) return split ? -95 : -75;
       per = m / 2;                                 // redo this part in halves
       P->fit_per = 0;                              // (and size the next call from the worst case again)
@@ -2577,8 +2514,7 @@ int xcg_pair_encode_stream(const XcgStreamArgs* a0, XcgPairState* P, int* rounds
     }
     const clk::time_point t3 = clk::now();
     const PairGpu G = gpu_of(a);
-    if (const int crc = pair_commit(P, G, st)) { done_scratch(); return crc == -75 ? -75 : -5; }
-    done_scratch();
+    if (const int crc = pair_commit(P, G, st)) return crc == -75 ? -75 : -5;
     if (pair_debug())
       fprintf(stderr, "pair: ms seed %.2f seed-replay %.2f parse %.2f replay %.2f commit %.2f (primary %u, clock %llu)\n",
               ms(t0, t1), ms(t1, t2), t_parse, t_replay, ms(t3, clk::now()), P->pcount,
