@@ -85,10 +85,18 @@ __device__ __forceinline__ uint32_t kbucket(uint32_t k) { return (k >> 3) & ((1u
 template <int LOGNB>
 __device__ __forceinline__ uint32_t kempty(uint32_t b) { return (~b & ((1u << LOGNB) - 1u)) << 3; }
 
-template <int LOGNB, int MAXD, int W>
+template <int LOGNB, int MAXD, int W, bool RING = false>
 struct IndepLDS {
   uint32_t key[W][2 << LOGNB];
   WaveRecs<LOGNB, MAXD, (MAXD <= 72)> rec[W];
+};
+// RING: each wave also stages its pieces' entering bytes through two 2 KiB
+// buffers (encode_chunk, "the input ring"), written by LDS-DMA loads.
+template <int LOGNB, int MAXD, int W>
+struct IndepLDS<LOGNB, MAXD, W, true> {
+  uint32_t key[W][2 << LOGNB];
+  WaveRecs<LOGNB, MAXD, (MAXD <= 72)> rec[W];
+  alignas(16) uint8_t ring[W][2][2048];
 };
 constexpr int GSLOTS_DECL = 8;   // = GSLOTS (pass-1 queue depth per lane)
 template <int LOGNB, int MAXD, int W>
@@ -296,6 +304,26 @@ __device__ __forceinline__ bool equal2048_regs(const uint8_t* a, const u32x4& w0
 // Make the registers of v live here (the compiler waits for their load first).
 __device__ __forceinline__ void vuse(const u32x4& v) {
   asm volatile("" ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]));
+}
+
+// The input ring (independent chunks): the entering bytes of the next two
+// contiguous pieces go global -> LDS without passing through registers, as a
+// linear image of the 2 KiB (lane l's two 16-byte loads read src + 16 l and
+// src + 1024 + 16 l: whole lines; the instruction offset applies to both
+// sides), non-temporal like the register loads.  hipcc does not count these
+// loads: the waits for them are written by hand (encode_chunk).
+typedef __attribute__((address_space(3))) uint8_t lds_u8;
+typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
+__device__ __forceinline__ void ring_load(const uint8_t* src, uint32_t lds_dst) {
+  uint32_t keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+      "global_load_lds_dwordx4 %1, off nt\n\t"
+      "global_load_lds_dwordx4 %1, off offset:1024 nt\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(src), "s"(lds_dst)
+      : "memory");
 }
 
 struct Piece {
@@ -654,10 +682,11 @@ struct GlbView {
   uint32_t* rsv;  // (stream) the wave's restart state, LDS: slot, old nev, nhits, olen, ndecl, restart ndecl
 };
 
-template <int LOGNB, int MAXD, bool STREAM, bool LRU = false>
+template <int LOGNB, int MAXD, bool STREAM, bool LRU = false, bool RING = false>
 __device__ __forceinline__ void encode_chunk(const EncParams& prm, char* kblk, const uint32_t kofs,
                                              WaveRecs<LOGNB, MAXD, (!STREAM && MAXD <= 72)>& T, const uint32_t chunk,
-                                             const GlbView gs) {
+                                             const GlbView gs, const lds_u8* ring = nullptr) {
+  static_assert(!RING || (!STREAM && MAXD <= 72), "the input ring belongs to the independent direct-mapped path");
   constexpr int NB = 1 << LOGNB;
   // independent chunks of up to 128 KiB: direct-mapped NX2 keys (roll_probe_dm)
   constexpr bool DM = !STREAM && MAXD <= 72;
@@ -733,6 +762,13 @@ __device__ __forceinline__ void encode_chunk(const EncParams& prm, char* kblk, c
   // prefetched B half.
   u32x4 nb0 = {0u, 0u, 0u, 0u}, nb1 = nb0;
   int nb_start = INT32_MIN;
+  // (RING) The input ring instead of nb*: buffer (p >> 11) & 1 holds the
+  // entering bytes of the piece at p.  rg_n = how many of the next contiguous
+  // pieces have theirs loaded or under way; rg_steady = whether each of the
+  // last two pieces issued a ring load and then the quiet steady state's
+  // three stores (bit 0: the latest piece).
+  int rg_n = 0;
+  uint32_t rg_steady = 0;
   // A candidate set at the piece start has its whole segment in the wave's A
   // registers; its EXTRACT body is written to the output right then, at the
   // offset the declaration will have if nothing cancels it (spec_olen).
@@ -1121,7 +1157,59 @@ __device__ __forceinline__ void encode_chunk(const EncParams& prm, char* kblk, c
     // here, inside their branch, and the prefetch below is waited for after
     // the vector phase -- never right behind its own issue.
     // (contig implies nb_start == p: the previous piece prefetched this B.)
-    if (contig) {
+    if constexpr (RING) {
+      const bool counted = rg_steady == 3u;
+      rg_steady = (rg_steady << 1) & 2u;
+      // (each register load is waited for in the branch that issued it: a
+      // wait the compiler places later would drain the ring loads too)
+      if (!contig) {
+        // first piece, or after a jump: the register path
+        P.a0 = piece_ld_safe<STREAM>(x, q0, L);
+        P.a1 = piece_ld_safe<STREAM>(x, q0 + 16, L);
+        P.b0 = piece_ld_safe<STREAM>(x, q0 + SEG, L);
+        P.b1 = piece_ld_safe<STREAM>(x, q0 + SEG + 16, L);
+        vuse(P.a0); vuse(P.a1); vuse(P.b0); vuse(P.b1);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (nothing of the ring in flight when it is primed again)
+        seg_sums(P.a0, P.a1, P.sxa, P.sqxa);
+        rg_n = 0;
+      } else {
+        P.a0 = P.b0; P.a1 = P.b1;
+        P.sxa = P.sxb; P.sqxa = P.sqxb;
+        if (rg_n > 0) {
+          // This piece's ring load was issued two pieces ago.  In the quiet
+          // steady state exactly eight vector memory operations are younger:
+          // the two pieces' three stores each (header, two body halves), and
+          // the two loads the previous piece issued.  vmcnt retires in order,
+          // so everything else stays in flight.  Any other history: wait for all.
+          if (counted) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+          else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          const lds_u8* rb = ring + ((((uint32_t)p >> 11) & 1u) << 11) + 32 * l;
+          P.b0 = *(const volatile lds_u32x4*)rb;
+          P.b1 = *(const volatile lds_u32x4*)(rb + 16);
+          --rg_n;
+        } else {
+          // a B half that reaches past the chunk (the guarded tail)
+          P.b0 = piece_ld_safe<STREAM>(x, q0 + SEG, L);
+          P.b1 = piece_ld_safe<STREAM>(x, q0 + SEG + 16, L);
+          vuse(P.b0); vuse(P.b1);
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+      }
+      // Fill the ring up to two pieces ahead, with loads that lie wholly
+      // inside the chunk (x + p is 16-byte aligned).  The buffer refilled in
+      // the steady state is the one just read: its reads return first.
+      const uint32_t ring_a = (uint32_t)(uintptr_t)ring;
+      const uint8_t* src = x + p + 16 * l;
+      if (rg_n == 0 && p + 3 * SEG <= L) {
+        ring_load(src + 2 * SEG, ring_a + (((((uint32_t)p >> 11) & 1u) ^ 1u) << 11));
+        rg_n = 1;
+      }
+      if (rg_n == 1 && p + 4 * SEG <= L) {
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(P.b0), "+v"(P.b1)::"memory");
+        ring_load(src + 3 * SEG, ring_a + ((((uint32_t)p >> 11) & 1u) << 11));
+        rg_n = 2;
+      }
+    } else if (contig) {
       P.a0 = P.b0; P.a1 = P.b1;
       P.sxa = P.sxb; P.sqxa = P.sqxb;
       P.b0 = nb0; P.b1 = nb1;
@@ -1157,7 +1245,7 @@ __device__ __forceinline__ void encode_chunk(const EncParams& prm, char* kblk, c
     // Prefetch the next contiguous piece's entering bytes; they land while
     // this piece rolls (issued after every use of this piece's loads).
     nb_start = p + SEG;
-    if (nb_start < last) {                         // (nb_start == last: decided as this piece's tail1 window)
+    if (!RING && nb_start < last) {                         // (nb_start == last: decided as this piece's tail1 window)
       if (p + 3 * SEG <= L) {                      // (uniform) every lane's 32 bytes inside the chunk: no guards
         nb0 = piece_ld<STREAM>(x + q0 + 2 * SEG);
         nb1 = piece_ld<STREAM>(x + q0 + 2 * SEG + 16);
@@ -1329,7 +1417,9 @@ __device__ __forceinline__ void encode_chunk(const EncParams& prm, char* kblk, c
 #ifdef XCG_PHASES
     const uint64_t tw0 = __builtin_amdgcn_s_memrealtime();
 #endif
-    vuse(nb0); vuse(nb1);                          // (unconditional: so the compiler sees them waited)
+    if constexpr (!RING) {
+      vuse(nb0); vuse(nb1);                        // (unconditional: so the compiler sees them waited)
+    }
 #ifdef XCG_PHASES
     ph_wait += __builtin_amdgcn_s_memrealtime() - tw0;
 #endif
@@ -1400,6 +1490,7 @@ __device__ __forceinline__ void encode_chunk(const EncParams& prm, char* kblk, c
       s = pe;
       insert_dm(cand_lo, cand_hi, (uint32_t)cand, k2, sl, readfirst(s0v));   // (its slot already read)
       c0_in_table = true;
+      if (RING && rg_n == 2) rg_steady |= 1u;       // (rg_n == 2: this piece issued the load two pieces ahead)
     }
     while (s < pe_x) {
       if (have_cand && cand + SEG <= s) declare(s);           // :183-190
@@ -1499,6 +1590,8 @@ __device__ __forceinline__ void encode_chunk(const EncParams& prm, char* kblk, c
     // pending candidate stays out of it until declared.
     totXA = totXB; totTA = totTB;
   }
+  // (an input ring load still in flight lands in this wave's LDS before the wave ends)
+  if constexpr (RING) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
   if (!spliced) {
     if (have_cand) declare(last + 1);                         // :257-261 (after every lookup)
@@ -1557,20 +1650,34 @@ __device__ __forceinline__ void encode_chunk(const EncParams& prm, char* kblk, c
 #ifndef XCG_INDEP_OCC
 #define XCG_INDEP_OCC 4
 #endif
+// The input ring of the 64 KiB / 128 KiB instance (0: the register prefetch);
+// its 4 KiB per wave come out of the key table, so that four workgroups still
+// share a CU's LDS.
+#ifndef XCG_INDEP_RING
+#define XCG_INDEP_RING 1
+#endif
 #ifndef XCG_INDEP_LOGNB
-#define XCG_INDEP_LOGNB 10
+#define XCG_INDEP_LOGNB (XCG_INDEP_RING ? 9 : 10)
 #endif
 #ifndef XCG_INDEP_W
 #define XCG_INDEP_W 4         // chunk-waves per workgroup
 #endif
 template <int LOGNB, int MAXD>
 __global__ __launch_bounds__(64 * XCG_INDEP_W, XCG_INDEP_OCC) void encode_independent_kernel(EncParams prm) {
-  __shared__ IndepLDS<LOGNB, MAXD, XCG_INDEP_W> S;
+  constexpr bool RING = XCG_INDEP_RING && MAXD <= 72;
+  __shared__ IndepLDS<LOGNB, MAXD, XCG_INDEP_W, RING> S;
+  static_assert(!RING || XCG_INDEP_OCC * sizeof(S) <= 160u * 1024u, "the workgroups of a CU share 160 KiB of LDS");
   const int wv = (int)readfirst(threadIdx.x >> 6);   // wave-uniform: keeps the parse state in SGPRs
   const uint32_t chunk = blockIdx.x * (uint32_t)XCG_INDEP_W + (uint32_t)wv;
   if (chunk >= prm.n) return;
-  encode_chunk<LOGNB, MAXD, false>(prm, (char*)S.key, (uint32_t)wv << (LOGNB + 3), S.rec[wv], chunk,
-                                   GlbView{nullptr, 0u, 0u, 0, nullptr, nullptr});
+  if constexpr (RING) {
+    encode_chunk<LOGNB, MAXD, false, false, true>(prm, (char*)S.key, (uint32_t)wv << (LOGNB + 3), S.rec[wv], chunk,
+                                                  GlbView{nullptr, 0u, 0u, 0, nullptr, nullptr},
+                                                  (const lds_u8*)&S.ring[wv][0][0]);
+  } else {
+    encode_chunk<LOGNB, MAXD, false>(prm, (char*)S.key, (uint32_t)wv << (LOGNB + 3), S.rec[wv], chunk,
+                                     GlbView{nullptr, 0u, 0u, 0, nullptr, nullptr});
+  }
 }
 
 // Stream semantics: persistent workgroups of SW waves share one LDS copy of
