@@ -315,7 +315,8 @@ int xcg_encode_call(xcg_ctx *ctx, const uint8_t *h_in, uint32_t len, uint8_t *h_
  * d_chunk_status[i]: 0 decoded, 1 blocked on an unknown REF (decode() returned
  * true with unknown hashes; later chunks get 2 = not reached), 3 partial op,
  * -1 bad opcode or BACKREF to an empty window slot (decode() returned false;
- * later chunks get 2).  h_unknown receives the sorted unknown hashes from the
+ * later chunks get 2); 4 (XCG_CHUNK_NOROOM) is xcg_decode_batch_independent's
+ * alone.  h_unknown receives the sorted unknown hashes from the
  * blocking point to the end of the batch (decode_skim, :196-272, over the
  * frames a pipe pair has buffered) for the ASK/LEARN protocol.
  * EXTRACTs decoded before the stop point enter the persistent cache
@@ -335,6 +336,58 @@ int xcg_decode_batch(xcg_ctx *ctx, const uint8_t *d_enc, const uint64_t *d_chunk
                      uint32_t n, uint32_t max_chunk_len, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off,
                      uint64_t *d_out_len, int32_t *d_chunk_status, uint64_t *d_consumed, uint64_t *h_unknown,
                      uint32_t unknown_cap, uint32_t *h_nunknown, uint64_t *h_total_out, void *stream);
+
+/*
+ * Decode n encoded chunks INDEPENDENTLY in one launch: the inverse of
+ * xcg_encode_batch(XCG_SEM_INDEPENDENT).  Chunk i is one
+ * XCodecDecoder::decode(output, input, unknown) call (xcodec/xcodec_decoder.cc:
+ * 66-188) on a decoder made for that chunk alone, with an empty
+ * XCodecMemoryCache and an empty XCodecWindow.  Nothing crosses chunks, and
+ * nothing is read from or written to the context's cache, pool, window or
+ * registry: the context supplies the device and the sticky status word.
+ * Asynchronous on `stream` (ordered behind the context's earlier calls); no
+ * host readback, no allocation.
+ * Chunk i is d_enc[d_chunk_off[i] .. + d_chunk_len[i]) and may write
+ * d_out[d_out_off[i] .. + d_out_cap[i]); any alignment of either.
+ * d_out_len[i] receives the decoded length.  d_chunk_status[i]:
+ *    0  decoded; d_consumed[i] == d_chunk_len[i].
+ *    1  decode() returned true on a REF whose hash has no EXTRACT earlier in
+ *       this chunk: d_consumed[i] is the REF's offset, d_out_len[i] the bytes
+ *       before it, d_first_unknown[i] (nullable array) that hash -- and 0 for
+ *       every chunk that did not block.
+ *    3  partial op at the end (a lone trailing F1 included); d_consumed[i] is
+ *       where it starts.
+ *   -1  bad opcode (d_consumed[i] at it), or BACKREF to an empty slot
+ *       (d_consumed[i] past it: the op has been moved out); decode() returned
+ *       false.  d_out_len[i] is what was decoded before.
+ *    4  XCG_CHUNK_NOROOM: the slot is too small.  d_out_len[i] is the size the
+ *       chunk needs, no byte outside the slot is written (bytes inside it are
+ *       unspecified), d_consumed[i] / d_first_unknown[i] are as if decoded; the
+ *       chunk's own status (0, 1, 3, -1) comes from a call with room.
+ * Status 2 (not reached) never occurs: an error or a block in one chunk does
+ * not touch the others.  Consumed and output bytes on 1 / 3 / -1 are exactly
+ * the reference's.  Name reuse inside a chunk (:106-136) is modelled on every
+ * context type: a later EXTRACT of a hash with other bytes replaces the entry,
+ * later REFs read the new bytes, the window keeps what each declare saw.
+ * The full decode_skim set (:196-272) is deliberately not produced: it serves
+ * ASK/LEARN, and a chunk without a peer cache has nobody to ask.  A caller who
+ * wants it runs that one chunk through xcg_decode_batch.
+ * max_chunk_len bounds every d_chunk_len[i] and is at most
+ * xcg_encode_bound(512 KiB) = 1 MiB + 16, the largest encode() output
+ * (XCG_EINVAL beyond; so are null pointers other than d_first_unknown); a
+ * longer chunk is refused with status -1 and bit 3 of the context's status
+ * word.  n == 0 is XCG_OK.  On a bounded or pair context: XCG_ENOTSUP when
+ * max_chunk_len / 2050 (the EXTRACTs a chunk can hold) exceeds the primary's
+ * limit in segments -- below that a fresh bounded cache never evicts.  The
+ * context's OOB / null-cache flags do not matter: the decoder's cache is
+ * always a fresh memory cache.
+ */
+#define XCG_CHUNK_NOROOM 4
+int xcg_decode_batch_independent(xcg_ctx *ctx, const uint8_t *d_enc, const uint64_t *d_chunk_off,
+                                 const uint32_t *d_chunk_len, uint32_t n, uint32_t max_chunk_len, uint8_t *d_out,
+                                 const uint64_t *d_out_off, const uint64_t *d_out_cap, uint64_t *d_out_len,
+                                 int32_t *d_chunk_status, uint64_t *d_consumed, uint64_t *d_first_unknown,
+                                 void *stream);
 
 /* A decoder's BACKREF window (XCodecWindow, xcodec/xcodec_window.h:40-125):
  * 256 slots of (hash, segment) that EXTRACT and REF declare into and

@@ -1478,6 +1478,33 @@ int xcg_decode_batch(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_chunk_o
   return rc;
 }
 
+int xcg_decode_batch_independent(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_chunk_off,
+                                 const uint32_t* d_chunk_len, uint32_t n, uint32_t max_chunk_len, uint8_t* d_out,
+                                 const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len,
+                                 int32_t* d_chunk_status, uint64_t* d_consumed, uint64_t* d_first_unknown,
+                                 void* stream) {
+  if (!c) return XCG_EINVAL;
+  if (n == 0) return XCG_OK;
+  if (!d_enc || !d_chunk_off || !d_chunk_len || !d_out || !d_out_off || !d_out_cap || !d_out_len || !d_chunk_status ||
+      !d_consumed)
+    return XCG_EINVAL;
+  if (max_chunk_len > xcg_encode_bound(1u << 19)) return XCG_EINVAL;
+  // A fresh bounded cache per chunk evicts nothing while the chunk's EXTRACTs
+  // fit the limit (at most max_chunk_len / 2050 of them); lookups enter nothing.
+  const uint32_t maxd = max_chunk_len / (2u + XCG_SEGMENT_LENGTH);
+  if ((c->bounded && maxd > c->lru.C) || (c->pair && maxd > c->pair_C)) return XCG_ENOTSUP;
+  DeviceGuard g(c->device);
+  ctx_order(c, (hipStream_t)stream);
+  XcgIndepDecodeArgs a{};
+  a.in = d_enc; a.chunk_off = d_chunk_off; a.chunk_len = d_chunk_len; a.n = n; a.max_len = max_chunk_len;
+  a.out = d_out; a.out_off = d_out_off; a.out_cap = d_out_cap; a.out_len = d_out_len;
+  a.chunk_status = d_chunk_status; a.consumed = d_consumed; a.first_unknown = d_first_unknown;
+  a.status = c->d_status;
+  const int rc = xcg_launch_decode_independent(&a, (hipStream_t)stream);
+  ctx_mark(c, (hipStream_t)stream);
+  return rc == -22 ? XCG_EINVAL : status_of(rc);
+}
+
 int xcg_debug_decode_reuse(xcg_ctx* c, uint64_t out[3]) {
   if (!c || !out) return XCG_EINVAL;
   const uint64_t* h = c->ds.h_scratch;

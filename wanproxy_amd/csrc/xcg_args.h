@@ -272,6 +272,25 @@ struct XcgDecodeArgs {
   uint32_t dup_cap;
 };
 
+// Arguments of the independent decode driver (xcg_launch_decode_independent):
+// per chunk its encoded bytes and the caller's output slot; nothing of a context
+// but its sticky status word.
+struct XcgIndepDecodeArgs {
+  const uint8_t* in;
+  const uint64_t* chunk_off;
+  const uint32_t* chunk_len;
+  uint32_t n;
+  uint32_t max_len;         // the caller's bound on every chunk length (picks the per-wave table size)
+  uint8_t* out;
+  const uint64_t* out_off;
+  const uint64_t* out_cap;
+  uint64_t* out_len;
+  int32_t* chunk_status;
+  uint64_t* consumed;
+  uint64_t* first_unknown;  // nullable
+  int32_t* status;
+};
+
 extern "C" int xcg_launch_encode_stream(const XcgStreamArgs* a, int* rounds_out, hipStream_t stream);
 extern "C" int xcg_lru_encode_stream(const XcgStreamArgs* a, XcgLruState* L, int* rounds_out, hipStream_t st);
 extern "C" int xcg_lru_times(const LruBatch* b, XcgLruState* L, hipStream_t st);
@@ -295,6 +314,7 @@ extern "C" int xcg_launch_pack(const uint8_t* src, const uint64_t* src_off, cons
                                uint8_t* dst, uint64_t* dst_off, uint64_t* d_total, hipStream_t stream);
 extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, uint64_t* block_pos_out,
                                  uint64_t* berr_pos_out, uint32_t* nunknown_out, hipStream_t stream);
+extern "C" int xcg_launch_decode_independent(const XcgIndepDecodeArgs* a, hipStream_t stream);
 extern "C" int xcg_launch_decode_small(const uint8_t* in, uint32_t len, const XcgCacheView* g, int32_t* status,
                                        void* scratch, uint32_t ops_cap, uint8_t* out, uint64_t out_cap,
                                        uint64_t* win_hash, uint8_t* win_seg, uint64_t win_count, uint64_t* res,

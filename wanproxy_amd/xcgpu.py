@@ -28,6 +28,7 @@ XCG_FLAG_NULLCACHE = 0x2
 XCG_SEM_INDEPENDENT = 0
 XCG_SEM_STREAM = 1
 XCG_EOVERFLOW = -75
+XCG_CHUNK_NOROOM = 4    # per-chunk status of xcg_decode_batch_independent: the output slot is too small
 
 _lib = None
 
@@ -120,6 +121,9 @@ def lib():
     L.xcg_decode_batch.argtypes = [vp, u8p, u64p, u32p, C.c_uint32, C.c_uint32, u8p, C.c_uint64, u64p, u64p, vp, u64p,
                                    u64p, C.c_uint32, vp, u64p, vp]
     L.xcg_decode_batch.restype = C.c_int
+    L.xcg_decode_batch_independent.argtypes = [vp, u8p, u64p, u32p, C.c_uint32, C.c_uint32, u8p, u64p, u64p, u64p, vp,
+                                               u64p, u64p, vp]
+    L.xcg_decode_batch_independent.restype = C.c_int
     L.xcg_window_create.argtypes = [vp, C.POINTER(C.c_void_p)]
     L.xcg_window_create.restype = C.c_int
     L.xcg_window_destroy.argtypes = [vp]
@@ -452,6 +456,74 @@ class Context:
         out = d_out.cpu().numpy()
         outs = [out[int(oo[i]):int(oo[i]) + int(ol[i])].tobytes() if st[i] != 2 else b'' for i in range(n)]
         return outs, st, cons, [int(u) for u in unk[:int(nunk[0])]]
+
+    def decode_batch_independent_device(self, d_enc, d_off, d_len, n, max_len, d_out, d_out_off, d_out_cap,
+                                        d_out_len, d_status, d_consumed, d_first_unknown=None, stream=None):
+        """Raw launch of xcg_decode_batch_independent on device tensors (all torch
+        tensors on this device); asynchronous on `stream`."""
+        _check(lib().xcg_decode_batch_independent(
+            self.h, C.c_void_p(d_enc.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(d_len.data_ptr()),
+            int(n), int(max_len), C.c_void_p(d_out.data_ptr()), C.c_void_p(d_out_off.data_ptr()),
+            C.c_void_p(d_out_cap.data_ptr()), C.c_void_p(d_out_len.data_ptr()), C.c_void_p(d_status.data_ptr()),
+            C.c_void_p(d_consumed.data_ptr()),
+            C.c_void_p(d_first_unknown.data_ptr()) if d_first_unknown is not None else None, _stream_ptr(stream)))
+
+    def decode_chunks_independent(self, encs, out_caps=None):
+        """Decode encoded chunks on the GPU, each on a fresh decoder of its own
+        (empty cache, empty window): the inverse of encode_chunks' independent
+        semantics.  out_caps: per-chunk slot sizes (default len * 205 + 4096, as
+        decode_chunks sizes its buffer); chunks whose slot was too small are
+        run once more with the size the kernel reported.  Returns (outs, status,
+        consumed, first_unknown) -- see xcg_decode_batch_independent."""
+        import torch
+        dev = torch.device('cuda', self.device)
+        n = len(encs)
+        st = np.zeros(n, dtype=np.int32)
+        cons = np.zeros(n, dtype=np.uint64)
+        unk = np.zeros(n, dtype=np.uint64)
+        outs = [b''] * n
+        if n == 0:
+            return outs, st, cons, unk
+        caps = (np.array([len(e) * 205 + 4096 for e in encs], dtype=np.uint64) if out_caps is None
+                else np.ascontiguousarray(out_caps, dtype=np.uint64))
+        todo = np.arange(n)
+        for attempt in range(2):
+            sub = [encs[i] for i in todo]
+            m = len(sub)
+            lens = np.array([len(e) for e in sub], dtype=np.uint32)
+            offs = np.zeros(m, dtype=np.uint64)
+            offs[1:] = np.cumsum(lens.astype(np.uint64))[:-1]
+            oo = np.zeros(m, dtype=np.uint64)
+            oo[1:] = np.cumsum(caps[todo])[:-1]
+            d_in = torch.from_numpy(np.frombuffer(b''.join(sub) or b'\0', dtype=np.uint8).copy()).to(dev)
+            d_off = torch.from_numpy(offs.view(np.int64)).to(dev)
+            d_len = torch.from_numpy(lens.view(np.int32)).to(dev)
+            d_oo = torch.from_numpy(oo.view(np.int64)).to(dev)
+            d_cap = torch.from_numpy(caps[todo].view(np.int64)).to(dev)
+            d_out = torch.zeros(max(int(caps[todo].sum()), 1), dtype=torch.uint8, device=dev)
+            d_ol = torch.zeros(m, dtype=torch.int64, device=dev)
+            d_st = torch.zeros(m, dtype=torch.int32, device=dev)
+            d_cons = torch.zeros(m, dtype=torch.int64, device=dev)
+            d_unk = torch.zeros(m, dtype=torch.int64, device=dev)
+            self.decode_batch_independent_device(d_in, d_off, d_len, m, int(lens.max()), d_out, d_oo, d_cap, d_ol,
+                                                 d_st, d_cons, d_unk)
+            torch.cuda.synchronize(dev)
+            self.status()
+            out = d_out.cpu().numpy()
+            ol = d_ol.cpu().numpy().view(np.uint64)
+            st[todo] = d_st.cpu().numpy()
+            cons[todo] = d_cons.cpu().numpy().view(np.uint64)
+            unk[todo] = d_unk.cpu().numpy().view(np.uint64)
+            for k, i in enumerate(todo):
+                if st[i] != XCG_CHUNK_NOROOM:
+                    outs[i] = out[int(oo[k]):int(oo[k]) + int(ol[k])].tobytes()
+            again = st[todo] == XCG_CHUNK_NOROOM
+            if attempt or not again.any():
+                break
+            caps = caps.copy()
+            caps[todo[again]] = ol[again]
+            todo = todo[again]
+        return outs, st, cons, unk
 
     def decode_call(self, data: bytes, out_cap: int = None):
         """One XCodecDecoder::decode(output, input, unknown) call from host memory
