@@ -99,6 +99,23 @@ def test_c5_large_chunks_cold_cache(filter_mode, stream_seed, oracle):
     ctx.close()
 
 
+def test_large_frames_past_two_waves_per_cu(oracle):
+    """Frames over 144 KiB (73+ declaration rows: the 264-record parse kernel)
+    in the smallest batch that gets six chunk-waves per workgroup instead of
+    two: 2 * CUs + 1 chunks of 144 KiB, checked chunk by chunk."""
+    import torch
+    from wanproxy_amd import synth
+    from wanproxy_amd.xcgpu import XCG_SEM_STREAM, Context
+    n = 2 * torch.cuda.get_device_properties(0).multi_processor_count + 1
+    data = synth.stream(0xB16, n * 144 * KiB, 20, 0)
+    offs, lens = synth.chunks_of(data, 144 * KiB)
+    exp = oracle.encode_batch(data, offs, lens, mode=1)
+    ctx = Context(0, cache_segments=1 << 16)
+    got = ctx.encode_chunks(data, offs, lens, semantics=XCG_SEM_STREAM)
+    assert first_diff(got, exp) is None
+    ctx.close()
+
+
 def test_mixed_alphabet_global_filter(filter_mode, stream_seed, oracle):
     """Collision-prone and 0xF1-heavy data through both filter modes."""
     from wanproxy_amd.synth import chunks_of

@@ -183,7 +183,7 @@ def test_independent_fuzz(oracle):
 
 def _dm_key(block):
     """The independent kernel's direct-mapped probe key of a 2048-byte window:
-    -(X2 + CLO) mod 2^32, X2 = sum (2048 - k) x_k (roll_probe_dm, xcg_encode.hip)."""
+    -(X2 + CLO) mod 2^32, X2 = sum (2048 - k) x_k (roll_probe_dm, xcg_encode_wave.h)."""
     w = np.arange(2048, 0, -1, dtype=np.uint64)
     x2 = int((w * block.astype(np.uint64)).sum()) & 0xFFFFFFFF
     return (-(x2 + 0x80200400)) & 0xFFFFFFFF

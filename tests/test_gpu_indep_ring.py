@@ -1,4 +1,4 @@
-"""The independent encoder's input ring (xcg_encode.hip, encode_chunk RING):
+"""The independent encoder's input ring (xcg_encode_wave.h, encode_chunk DM):
 the entering bytes of a chunk's contiguous pieces are staged global -> LDS two
 pieces ahead, in two 2 KiB buffers per wave, and taken out behind a counted
 wait.  What can go wrong is a piece reading a buffer that holds another
@@ -179,7 +179,7 @@ def test_mixed_lengths_128k_with_duplicates(ctx, oracle):
 
 def _dm_key(block):
     """The direct-mapped probe key of a 2048-byte window: -(X2 + CLO) mod 2^32,
-    X2 = sum (2048 - k) x_k (roll_probe_dm, xcg_encode.hip)."""
+    X2 = sum (2048 - k) x_k (roll_probe_dm, xcg_encode_wave.h)."""
     w = np.arange(2048, 0, -1, dtype=np.uint64)
     x2 = int((w * block.astype(np.uint64)).sum()) & 0xFFFFFFFF
     return (-(x2 + 0x80200400)) & 0xFFFFFFFF

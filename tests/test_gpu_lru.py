@@ -78,6 +78,26 @@ def test_lru_random_vs_oracle(oracle, stream_seed, limit_segs, chunk):
     assert gsize == esize
 
 
+@pytest.mark.parametrize('chunk,cu_mult', [(4096, 4), (4096, 8), (144 * 1024, 2)])
+def test_lru_batch_past_wave_count_boundary(oracle, chunk, cu_mult):
+    """The smallest batch past each boundary at which the stream parse kernel
+    gets more chunk-waves per workgroup (cu_mult * CUs + 1 chunks: 8 and 16
+    waves for small chunks, 6 for frames over 144 KiB), as the first call on a
+    cache that holds it in one sub-batch; a second call then evicts."""
+    import torch
+    from wanproxy_amd import synth
+    n = cu_mult * torch.cuda.get_device_properties(0).multi_processor_count + 1
+    more = n if chunk == 4096 else 40
+    limit = (n * (chunk // SEG + 1) + 64) * SEG
+    d = synth.stream(0x1B0 + cu_mult, (n + more) * chunk, 5, 0)
+    offs, lens = synth.chunks_of(d, chunk)
+    exp, esize = oracle_stream(oracle, d, offs, lens, limit)
+    got, gsize = gpu_stream(d, offs, lens, limit, steps=[n, more])
+    bad = [i for i in range(len(exp)) if got[i] != exp[i]]
+    assert not bad, (chunk, n, bad[:8])
+    assert gsize == esize
+
+
 def test_lru_split_batches(oracle):
     # The cache (and its LRU order) persists across calls.
     from wanproxy_amd.synth import chunks_of

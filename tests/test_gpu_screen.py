@@ -1,4 +1,4 @@
-"""The quiet-chunk screen of small stream chunks (xcg_encode.hip
+"""The quiet-chunk screen of small stream chunks (xcg_encode_screen.hip
 stream_screen_kernel): chunks none of whose windows can be found get the cold
 parse (the 2048-byte tiling) without the state machine, the rest are parsed.
 Every case is encoded with the screen on and off and both equal the oracle's

@@ -11,7 +11,9 @@ import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRCS = ['csrc/xcg_api.hip', 'csrc/xcg_encode.hip', 'csrc/xcg_decode.hip', 'csrc/xcg_decode_indep.hip',
+# (the encoder's units first: the two stream units are the longest compiles)
+SRCS = ['csrc/xcg_encode_stream.hip', 'csrc/xcg_encode_stream_lru.hip', 'csrc/xcg_encode_indep.hip',
+        'csrc/xcg_encode_screen.hip', 'csrc/xcg_api.hip', 'csrc/xcg_decode.hip', 'csrc/xcg_decode_indep.hip',
         'csrc/xcg_hash.hip', 'csrc/xcg_lru.hip', 'csrc/xcg_pair.hip', 'csrc/xcg_pipe.cpp', 'csrc/xcg_deflate.hip',
         'csrc/xcg_inflate.hip']
 HDRS = sorted(glob.glob(os.path.join(HERE, 'csrc', '*.h'))) + ['../include/xcgpu.h']   # every object depends on all
@@ -48,9 +50,10 @@ def build_lib(force: bool = False, verbose: bool = False, out: str = OUT, define
         os.replace(obj + '.tmp', obj)
         return obj
 
-    with ThreadPoolExecutor(min(len(srcs), os.cpu_count() or 1)) as ex:
+    with ThreadPoolExecutor(min(len(srcs), os.cpu_count() or 1, 16)) as ex:
         objs = list(ex.map(compile_one, srcs))
-    cmd = [HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', out + '.tmp'] + objs
+    # -z defs: a function one unit declares and none defines fails here, not at its first call
+    cmd = [HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC', '-Wl,-z,defs', '-o', out + '.tmp'] + objs
     if verbose:
         print(' '.join(cmd))
     subprocess.run(cmd, check=True, cwd=HERE)

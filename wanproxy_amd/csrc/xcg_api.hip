@@ -76,7 +76,7 @@ struct BatchScratch {
   uint32_t* enter_base = nullptr;  // n_cap + 1
   uint32_t* ev_slot = nullptr;     // n_cap * maxe: each reference's pool slot / LRU time
   uint64_t* ev_time = nullptr;
-  // re-parse restart (xcg_encode.hip RestartArgs): REF output lengths, the
+  // re-parse restart (xcg_encode_wave.h RestartArgs): REF output lengths, the
   // contradicted-lookup times, and a backup of the flagged chunks' rows
   uint32_t* eo = nullptr;          // n_cap * maxe
   uint32_t* bad_t = nullptr;       // n_cap
@@ -146,7 +146,7 @@ struct xcg_ctx {
   // stream): the cache-inspection calls wait for this event only, never for
   // the whole device, so other contexts and streams keep running.
   hipEvent_t done_ev = nullptr;
-  hipEvent_t flags_ev = nullptr;   // stream batches: behind the verification flags' copy (xcg_encode.hip)
+  hipEvent_t flags_ev = nullptr;   // stream batches: behind the verification flags' copy (xcg_encode_stream.hip)
   XcgPairState* pair = nullptr;   // XCodecCachePair(memory, disk) (xcg_pair.hip): a front of a disk
   uint32_t pair_C = 0;             // its primary limit in segments
   bool no_window = false;          // (single-segment host calls: decodes that leave the window alone)

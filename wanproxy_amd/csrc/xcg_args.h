@@ -1,6 +1,6 @@
 // The library's internal interface: every struct and every extern "C" function
 // that crosses translation units inside libxcgpu (the host ABI layer
-// xcg_api.hip, xcg_pipe.cpp and the kernel drivers xcg_encode / xcg_decode /
+// xcg_api.hip, xcg_pipe.cpp and the kernel drivers xcg_encode_* / xcg_decode /
 // xcg_lru / xcg_pair / xcg_hash).  The file that defines one of these functions
 // and every file that calls it include this header, so a prototype that drifts
 // is a compile error.  Plain data only: xcg_pipe.cpp compiles it as host C++.
@@ -302,6 +302,19 @@ extern "C" int xcg_launch_encode_independent(const uint8_t* d_in, const uint64_t
                                              uint32_t flags, uint8_t* d_out, const uint64_t* d_out_off,
                                              uint64_t* d_out_len, uint32_t* d_stats, int32_t* d_status,
                                              hipStream_t stream);
+// Between the encoder's units, for the stream round driver (xcg_encode_stream.hip;
+// EncParams: xcg_encode_wave.h).  The parse kernel's reference-recording
+// instance for (big, SW) (xcg_encode_stream_lru.hip), and the quiet-chunk
+// screen in front of a parse: a->s_work cleared, the fold, the screen and its
+// finish, which leaves the chunks still to parse in a->s_work (xcg_encode_screen.hip).
+namespace xcg {
+struct EncParams;
+constexpr int SCREEN_MAXD = 4;   // the screen takes chunks shorter than 4 tiles (< 8 KiB; s_rows: 4 rows a chunk)
+}
+extern "C" void xcg_launch_encode_stream_lru(int big, uint32_t SW, dim3 grid, dim3 block, const xcg::EncParams* prm,
+                                             hipStream_t stream);
+extern "C" void xcg_launch_stream_screen(const XcgStreamArgs* a, const xcg::EncParams* prm, uint32_t wgs,
+                                         hipStream_t stream);
 
 extern "C" int xcg_launch_window_hashes(const uint8_t* d_x, uint64_t len, uint64_t* d_hash, hipStream_t stream);
 extern "C" int xcg_launch_segment_hashes(const uint8_t* d_x, uint64_t len, uint64_t* d_hash, hipStream_t stream);

@@ -24,7 +24,7 @@ constexpr uint32_t FILT_WORDS = (1u << FILT_LOG2) / 32;
 // A round's LDS lane filter comes in PREFIX_FILTERS slices: slice j holds the
 // cache and the batch declarations of chunks < (j + 1) * pfdiv, so a workgroup
 // whose chunks all lie below that copies slice j -- on average half the
-// batch's keys, and far fewer for the first chunks (xcg_encode.hip
+// batch's keys, and far fewer for the first chunks (xcg_encode_stream.hip
 // filt_prefix_kernel).
 constexpr uint32_t PREFIX_FILTERS = 16;
 constexpr uint32_t FOVF16 = 2u;                     // bucket-overflow flag in slot 7 (even: never a fingerprint)

@@ -1,0 +1,52 @@
+// XCodec encoder, independent chunks: one wave per chunk runs encode_chunk
+// (xcg_encode_wave.h) against a table of the chunk's own declarations.
+#include "xcg_encode_wave.h"
+
+namespace xcg {
+
+// INDEP_W chunk-waves per workgroup, INDEP_OCC workgroups per CU: four waves
+// per SIMD, one resident wave per chunk of a 4096-chunk launch.
+constexpr int INDEP_W = 4;
+constexpr int INDEP_OCC = 4;
+// The 64 KiB / 128 KiB instance's direct-mapped key table: 2 << 9 = 1024 slots
+// per wave.  The input ring's 4 KiB per wave came out of it (2048 slots before),
+// so a workgroup stays at 36,736 B and four share a CU's LDS; the smaller table
+// alone measured +0.4 %, the ring 0.942 of the register prefetch's time
+// (profiles/indep_ring_ab.txt).
+constexpr int INDEP_LOGNB = 9;
+
+template <int LOGNB, int MAXD>
+__global__ __launch_bounds__(64 * INDEP_W, INDEP_OCC) void encode_independent_kernel(EncParams prm) {
+  __shared__ IndepLDS<LOGNB, MAXD, INDEP_W> S;
+  static_assert(MAXD > 72 || INDEP_OCC * sizeof(S) <= 160u * 1024u, "the workgroups of a CU share 160 KiB of LDS");
+  const int wv = (int)readfirst(threadIdx.x >> 6);   // wave-uniform: keeps the parse state in SGPRs
+  const uint32_t chunk = blockIdx.x * (uint32_t)INDEP_W + (uint32_t)wv;
+  if (chunk >= prm.n) return;
+  encode_chunk<LOGNB, MAXD, false>(prm, (char*)S.key, (uint32_t)wv << (LOGNB + 3), S.rec[wv], chunk,
+                                   GlbView{nullptr, 0u, 0u, 0, nullptr, nullptr}, S.ring_of(wv));
+}
+
+template __global__ void encode_independent_kernel<INDEP_LOGNB, 72>(EncParams);
+template __global__ void encode_independent_kernel<11, 264>(EncParams);
+
+}  // namespace xcg
+
+extern "C" int xcg_launch_encode_independent(const uint8_t* d_in, const uint64_t* d_chunk_off,
+                                             const uint32_t* d_chunk_len, uint32_t n, uint32_t max_chunk_len,
+                                             uint32_t flags, uint8_t* d_out, const uint64_t* d_out_off,
+                                             uint64_t* d_out_len, uint32_t* d_stats, int32_t* d_status,
+                                             hipStream_t stream) {
+  using namespace xcg;
+  if (n == 0) return 0;
+  EncParams prm{d_in, d_chunk_off, d_chunk_len, n, flags, d_out, d_out_off, d_out_len, d_stats, d_status};
+  prm.max_len = max_chunk_len;
+  dim3 grid((n + INDEP_W - 1) / INDEP_W), block(64 * INDEP_W);
+  if (max_chunk_len <= (1u << 17)) {
+    hipLaunchKernelGGL((encode_independent_kernel<INDEP_LOGNB, 72>), grid, block, 0, stream, prm);
+  } else if (max_chunk_len <= (1u << 19)) {
+    hipLaunchKernelGGL((encode_independent_kernel<11, 264>), grid, block, 0, stream, prm);
+  } else {
+    return -22;
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
