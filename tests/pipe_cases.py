@@ -26,6 +26,8 @@ import hashlib
 import random
 from collections import namedtuple
 
+from collision_cases import family  # noqa: F401  (segments of one XCodecHash; used below and by importers)
+
 SEG = 2048
 FRAME_IN = 512 * 1024                 # XCODEC_PIPE_MAX_FRAME / 2: input bytes per frame
 
@@ -63,22 +65,6 @@ def mixed(seed: int, n: int, pool: int = 150, repeat: float = 0.55) -> bytes:
         else:
             out += bytes(0xF1 if b < 128 else b for b in r.randbytes(r.randrange(1, 400)))
     return bytes(out[:n])
-
-
-def family(seed: int, nvar: int = 3):
-    """`nvar` distinct segments of one XCodecHash (as tests/test_gpu_decode_reuse.py):
-    a seeded base of odd bytes in 7..201, variant j with +2, -4, +2 at 100 + 40 j."""
-    r = random.Random(seed)
-    base = bytearray(r.randrange(7, 202, 2) for _ in range(SEG))
-    out = []
-    for j in range(nvar):
-        v = bytearray(base)
-        o = 100 + 40 * j
-        v[o] += 2
-        v[o + 1] -= 4
-        v[o + 2] += 2
-        out.append(bytes(v))
-    return out
 
 
 # ---------------------------------------------------------------- wire helpers

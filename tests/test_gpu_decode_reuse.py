@@ -18,6 +18,7 @@ import random
 import pytest
 
 from backref_streams import WindowModel
+from collision_cases import family  # noqa: F401  (re-exported)
 from golden_cases import data
 
 pytestmark = pytest.mark.gpu
@@ -39,22 +40,6 @@ def BR(i):
 
 def LIT(b):
     return b.replace(b'\xf1', b'\xf1\x00')
-
-
-def family(seed, nvar=3):
-    """`nvar` distinct segments of one XCodecHash: a seeded base of odd bytes in
-    7..201, variant j with +2, -4, +2 at offset 100 + 40 j."""
-    r = random.Random(seed)
-    base = bytearray(r.randrange(7, 202, 2) for _ in range(SEG))
-    out = []
-    for j in range(nvar):
-        v = bytearray(base)
-        o = 100 + 40 * j
-        v[o] += 2
-        v[o + 1] -= 4
-        v[o + 2] += 2
-        out.append(bytes(v))
-    return out
 
 
 def filler(seed):

@@ -9,8 +9,9 @@ bytes, out_len and stats words with the CPU oracle (mode 0), and decodes the
 result back to the input.
 
 The oracle gives no stats words: n_extract and n_ref (words 0, 1) are counted
-from the oracle's own output ops; n_collision (word 2) is 0 for random bytes
-(a collision needs two different segments with one 64-bit hash); n_pieces
+from the oracle's own output ops; n_collision (word 2) is 0 here, since random
+bytes hold no two different segments with one 64-bit hash (constructed
+collisions and their non-zero counts: tests/test_gpu_collisions.py); n_pieces
 (word 3) is the kernel's own piece count, bounded below by the windows it has
 to cover in pieces of 2048 positions (a REF skips 2048 of them)."""
 import numpy as np
