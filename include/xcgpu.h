@@ -389,6 +389,74 @@ int xcg_decode_batch_independent(xcg_ctx *ctx, const uint8_t *d_enc, const uint6
                                  int32_t *d_chunk_status, uint64_t *d_consumed, uint64_t *d_first_unknown,
                                  void *stream);
 
+/*
+ * Encode n chunks as MANY SHORT STREAMS in one launch: the semantics between
+ * XCG_SEM_INDEPENDENT (a fresh cache per chunk) and XCG_SEM_STREAM (one
+ * persistent cache per batch).  d_group_first is a device array of
+ * n_groups + 1 ascending values from 0 to n; group g is the consecutive
+ * chunks [d_group_first[g], d_group_first[g + 1]) and may be empty.  The
+ * chunks of a group, in order, are successive XCodecEncoder::encode calls
+ * (xcodec/xcodec_encoder.cc:74-274) of one encoder whose cache is a fresh,
+ * empty XCodecMemoryCache made for that group (xcodec_cache.h:303-365): chunk
+ * k sees every declaration of the group's chunks < k and its own, with the
+ * reference's exact rules (REF on byte equality, collision skip otherwise,
+ * :374-416) -- what `tack -c` does over one file (programs/tack/tack.cc:301-321)
+ * or a proxy over one short connection.  Nothing crosses groups, and nothing is
+ * read from or written to the context's cache, pool or registry: the context
+ * supplies the device, the flags (XCG_FLAG_OOB / XCG_FLAG_NULLCACHE act as in
+ * XCG_SEM_INDEPENDENT) and the sticky status word.  Asynchronous on `stream`
+ * (ordered behind the context's earlier calls); no host readback, no allocation.
+ * Chunks lie anywhere in d_in at any alignment; slots, d_out_len and d_stats
+ * are per chunk, as in xcg_encode_batch (d_stats of a chunk < 2048 bytes: 0).
+ * max_group_len bounds the SUM of each group's chunk lengths and is at most
+ * 512 KiB, so a group makes at most 256 declarations (XCG_EINVAL beyond; so
+ * are null pointers other than d_stats).  A group whose lengths sum past
+ * max_group_len is refused as a whole, never parsed: d_out_len 0 for all its
+ * chunks and bit 3 of the context's status word; so is a group whose
+ * d_group_first entries do not ascend within [0, n] (it names no chunks:
+ * nothing is written for it).  Other groups of the launch are unaffected.
+ * n == 0 or n_groups == 0 is XCG_OK.  On a bounded or pair context:
+ * XCG_ENOTSUP when max_group_len / 2048 exceeds the primary's limit in
+ * segments -- below that a fresh bounded cache never evicts.
+ */
+int xcg_encode_batch_grouped(xcg_ctx *ctx, const uint8_t *d_in, const uint64_t *d_chunk_off,
+                             const uint32_t *d_chunk_len, uint32_t n, const uint32_t *d_group_first,
+                             uint32_t n_groups, uint32_t max_group_len, uint8_t *d_out,
+                             const uint64_t *d_out_off, uint64_t *d_out_len, uint32_t *d_stats, void *stream);
+
+/*
+ * The inverse: the chunks of a group, in order, are successive
+ * XCodecDecoder::decode calls (xcodec/xcodec_decoder.cc:66-188) on one decoder
+ * made for that group, with an empty XCodecMemoryCache and an empty
+ * XCodecWindow.  The cache and the window live across the group's chunks: name
+ * reuse (:106-136), the BACKREF slots and the cursor (:165-181), so a REF or
+ * BACKREF may name an EXTRACT of an earlier chunk of its group.  Slots, lengths,
+ * statuses 0 / 1 / 3 / -1 / 4, d_consumed and d_first_unknown are per chunk and
+ * mean what they mean in xcg_decode_batch_independent.  One stream rule is
+ * added: the group stops at the first chunk whose OWN status (what a call with
+ * room would report, so also a status-4 chunk whose real status is 1, 3 or -1)
+ * is not 0; every later chunk of the group gets status 2 (not reached), length
+ * 0, consumed 0, first-unknown 0, as xcg_decode_batch reports past its blocking
+ * point.  A chunk that is only out of room (status 4, own status 0) does not
+ * stop the group: the walk went on, the cache and window evolved, and later
+ * chunks read their segments from the input.  decode_skim's set is not produced.
+ * max_group_len bounds the sum of each group's chunk lengths and is at most
+ * xcg_encode_bound(512 KiB) = 1 MiB + 16 (XCG_EINVAL beyond; so are null
+ * pointers other than d_first_unknown).  A group whose lengths sum past it, or
+ * whose sum of floor(len / 2050) would half fill the per-group table, is refused
+ * as a whole before anything is written: status -1, length 0, consumed 0 for
+ * its chunks and bit 3 of the context's status word; a group whose
+ * d_group_first entries do not ascend within [0, n] sets the bit and writes
+ * nothing.  XCG_ENOTSUP on a bounded or pair context when max_group_len / 2050
+ * exceeds the primary's limit in segments.  The context's flags do not matter.
+ */
+int xcg_decode_batch_grouped(xcg_ctx *ctx, const uint8_t *d_enc, const uint64_t *d_chunk_off,
+                             const uint32_t *d_chunk_len, uint32_t n, const uint32_t *d_group_first,
+                             uint32_t n_groups, uint32_t max_group_len, uint8_t *d_out,
+                             const uint64_t *d_out_off, const uint64_t *d_out_cap, uint64_t *d_out_len,
+                             int32_t *d_chunk_status, uint64_t *d_consumed, uint64_t *d_first_unknown,
+                             void *stream);
+
 /* A decoder's BACKREF window (XCodecWindow, xcodec/xcodec_window.h:40-125):
  * 256 slots of (hash, segment) that EXTRACT and REF declare into and
  * <BACKREF> index reads (xcodec/xcodec_decoder.cc:137,160,165-181).  It lives

@@ -7,23 +7,43 @@ from __future__ import annotations
 
 import glob
 import os
+import re
 import subprocess
+import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # (the encoder's units first: the two stream units are the longest compiles)
 SRCS = ['csrc/xcg_encode_stream.hip', 'csrc/xcg_encode_stream_lru.hip', 'csrc/xcg_encode_indep.hip',
-        'csrc/xcg_encode_screen.hip', 'csrc/xcg_api.hip', 'csrc/xcg_decode.hip', 'csrc/xcg_decode_indep.hip',
-        'csrc/xcg_hash.hip', 'csrc/xcg_lru.hip', 'csrc/xcg_pair.hip', 'csrc/xcg_pipe.cpp', 'csrc/xcg_deflate.hip',
-        'csrc/xcg_inflate.hip']
+        'csrc/xcg_encode_group.hip', 'csrc/xcg_encode_screen.hip', 'csrc/xcg_api.hip', 'csrc/xcg_decode.hip',
+        'csrc/xcg_decode_indep.hip', 'csrc/xcg_decode_group.hip', 'csrc/xcg_hash.hip', 'csrc/xcg_lru.hip',
+        'csrc/xcg_pair.hip', 'csrc/xcg_pipe.cpp', 'csrc/xcg_deflate.hip', 'csrc/xcg_inflate.hip']
 HDRS = sorted(glob.glob(os.path.join(HERE, 'csrc', '*.h'))) + ['../include/xcgpu.h']   # every object depends on all
 OUT = os.path.join(HERE, 'libxcgpu.so')
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+# Units whose kernels keep their whole parse state in registers: a compiler that spills it
+# to scratch still builds a correct library, several times slower, and no test would notice -- so the build reads
+# these units' resource-usage remarks and refuses a kernel with scratch.
+NO_SCRATCH = ('csrc/xcg_encode_indep.hip', 'csrc/xcg_encode_group.hip')
+REMARKS = '-Rpass-analysis=kernel-resource-usage'
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall'] + os.environ.get('XCG_EXTRA_FLAGS', '').split()
 
 
 def _newer(out: str, deps) -> bool:
     return os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in deps)
+
+
+def scratch_of(remarks: str) -> dict:
+    """kernel name -> scratch bytes per lane, from hipcc's kernel-resource-usage remarks."""
+    out, name = {}, None
+    for line in remarks.splitlines():
+        m = re.search(r'remark: +Function Name: (\S+)', line)
+        if m:
+            name = m.group(1)
+        m = re.search(r'remark: +ScratchSize \[bytes/lane\]: (\d+)', line)
+        if m and name is not None:
+            out[name] = int(m.group(1))
+    return out
 
 
 def build_lib(force: bool = False, verbose: bool = False, out: str = OUT, defines=()) -> str:
@@ -43,10 +63,19 @@ def build_lib(force: bool = False, verbose: bool = False, out: str = OUT, define
         obj = os.path.join(objdir, os.path.basename(src) + tag + '.o')
         if not force and _newer(obj, [src] + hdrs):
             return obj
-        cmd = [HIPCC] + FLAGS + dflags + ['-c', '-o', obj + '.tmp', src]
+        checked = os.path.relpath(src, HERE) in NO_SCRATCH
+        cmd = [HIPCC] + FLAGS + ([REMARKS] if checked else []) + dflags + ['-c', '-o', obj + '.tmp', src]
         if verbose:
             print(' '.join(cmd))
-        subprocess.run(cmd, check=True, cwd=HERE)
+        if checked:
+            r = subprocess.run(cmd, check=True, cwd=HERE, stderr=subprocess.PIPE, text=True)
+            sys.stderr.write(''.join(ln + '\n' for ln in r.stderr.splitlines() if 'remark:' not in ln))
+            usage = scratch_of(r.stderr)
+            spilled = {k: v for k, v in usage.items() if v}
+            if not usage or spilled:
+                raise RuntimeError('%s: kernels with scratch (or no remarks at all): %s' % (src, spilled))
+        else:
+            subprocess.run(cmd, check=True, cwd=HERE)
         os.replace(obj + '.tmp', obj)
         return obj
 

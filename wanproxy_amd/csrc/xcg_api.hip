@@ -1505,6 +1505,55 @@ int xcg_decode_batch_independent(xcg_ctx* c, const uint8_t* d_enc, const uint64_
   return rc == -22 ? XCG_EINVAL : status_of(rc);
 }
 
+int xcg_encode_batch_grouped(xcg_ctx* c, const uint8_t* d_in, const uint64_t* d_chunk_off,
+                             const uint32_t* d_chunk_len, uint32_t n, const uint32_t* d_group_first,
+                             uint32_t n_groups, uint32_t max_group_len, uint8_t* d_out, const uint64_t* d_out_off,
+                             uint64_t* d_out_len, uint32_t* d_stats, void* stream) {
+  if (!c) return XCG_EINVAL;
+  if (n == 0 || n_groups == 0) return XCG_OK;
+  if (!d_in || !d_chunk_off || !d_chunk_len || !d_group_first || !d_out || !d_out_off || !d_out_len)
+    return XCG_EINVAL;
+  if (max_group_len > (1u << 19)) return XCG_EINVAL;
+  // A fresh bounded cache per group evicts nothing while the group's
+  // declarations fit the limit (at most max_group_len / 2048 of them).
+  const uint32_t maxd = max_group_len / XCG_SEGMENT_LENGTH;
+  if ((c->bounded && maxd > c->lru.C) || (c->pair && maxd > c->pair_C)) return XCG_ENOTSUP;
+  DeviceGuard g(c->device);
+  ctx_order(c, (hipStream_t)stream);
+  const int rc = xcg_launch_encode_group(d_in, d_chunk_off, d_chunk_len, n, d_group_first, n_groups, max_group_len,
+                                         c->flags, d_out, d_out_off, d_out_len, d_stats, c->d_status,
+                                         (hipStream_t)stream);
+  ctx_mark(c, (hipStream_t)stream);
+  return rc == -22 ? XCG_EINVAL : status_of(rc);
+}
+
+int xcg_decode_batch_grouped(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_chunk_off,
+                             const uint32_t* d_chunk_len, uint32_t n, const uint32_t* d_group_first,
+                             uint32_t n_groups, uint32_t max_group_len, uint8_t* d_out, const uint64_t* d_out_off,
+                             const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_chunk_status,
+                             uint64_t* d_consumed, uint64_t* d_first_unknown, void* stream) {
+  if (!c) return XCG_EINVAL;
+  if (n == 0 || n_groups == 0) return XCG_OK;
+  if (!d_enc || !d_chunk_off || !d_chunk_len || !d_group_first || !d_out || !d_out_off || !d_out_cap || !d_out_len ||
+      !d_chunk_status || !d_consumed)
+    return XCG_EINVAL;
+  if (max_group_len > xcg_encode_bound(1u << 19)) return XCG_EINVAL;
+  // (the independent call's rule: at most max_group_len / 2050 EXTRACTs enter a group's cache)
+  const uint32_t maxd = max_group_len / (2u + XCG_SEGMENT_LENGTH);
+  if ((c->bounded && maxd > c->lru.C) || (c->pair && maxd > c->pair_C)) return XCG_ENOTSUP;
+  DeviceGuard g(c->device);
+  ctx_order(c, (hipStream_t)stream);
+  XcgGroupDecodeArgs a{};
+  a.in = d_enc; a.chunk_off = d_chunk_off; a.chunk_len = d_chunk_len; a.n = n;
+  a.group_first = d_group_first; a.n_groups = n_groups; a.max_len = max_group_len;
+  a.out = d_out; a.out_off = d_out_off; a.out_cap = d_out_cap; a.out_len = d_out_len;
+  a.chunk_status = d_chunk_status; a.consumed = d_consumed; a.first_unknown = d_first_unknown;
+  a.status = c->d_status;
+  const int rc = xcg_launch_decode_group(&a, (hipStream_t)stream);
+  ctx_mark(c, (hipStream_t)stream);
+  return rc == -22 ? XCG_EINVAL : status_of(rc);
+}
+
 int xcg_debug_decode_reuse(xcg_ctx* c, uint64_t out[3]) {
   if (!c || !out) return XCG_EINVAL;
   const uint64_t* h = c->ds.h_scratch;

@@ -291,6 +291,26 @@ struct XcgIndepDecodeArgs {
   int32_t* status;
 };
 
+// Arguments of the grouped decode driver (xcg_launch_decode_group): the same,
+// with the chunks partitioned into groups of consecutive chunks, one decoder each.
+struct XcgGroupDecodeArgs {
+  const uint8_t* in;
+  const uint64_t* chunk_off;
+  const uint32_t* chunk_len;
+  uint32_t n;
+  const uint32_t* group_first;  // [n_groups + 1] ascending, 0 .. n
+  uint32_t n_groups;
+  uint32_t max_len;         // the caller's bound on every group's summed chunk lengths (picks the table size)
+  uint8_t* out;
+  const uint64_t* out_off;
+  const uint64_t* out_cap;
+  uint64_t* out_len;
+  int32_t* chunk_status;
+  uint64_t* consumed;
+  uint64_t* first_unknown;  // nullable
+  int32_t* status;
+};
+
 extern "C" int xcg_launch_encode_stream(const XcgStreamArgs* a, int* rounds_out, hipStream_t stream);
 extern "C" int xcg_lru_encode_stream(const XcgStreamArgs* a, XcgLruState* L, int* rounds_out, hipStream_t st);
 extern "C" int xcg_lru_times(const LruBatch* b, XcgLruState* L, hipStream_t st);
@@ -302,6 +322,12 @@ extern "C" int xcg_launch_encode_independent(const uint8_t* d_in, const uint64_t
                                              uint32_t flags, uint8_t* d_out, const uint64_t* d_out_off,
                                              uint64_t* d_out_len, uint32_t* d_stats, int32_t* d_status,
                                              hipStream_t stream);
+extern "C" int xcg_launch_encode_group(const uint8_t* d_in, const uint64_t* d_chunk_off, const uint32_t* d_chunk_len,
+                                       uint32_t n, const uint32_t* d_group_first, uint32_t n_groups,
+                                       uint32_t max_group_len, uint32_t flags, uint8_t* d_out,
+                                       const uint64_t* d_out_off, uint64_t* d_out_len, uint32_t* d_stats,
+                                       int32_t* d_status, hipStream_t stream);
+extern "C" int xcg_launch_decode_group(const XcgGroupDecodeArgs* a, hipStream_t stream);
 // Between the encoder's units, for the stream round driver (xcg_encode_stream.hip;
 // EncParams: xcg_encode_wave.h).  The parse kernel's reference-recording
 // instance for (big, SW) (xcg_encode_stream_lru.hip), and the quiet-chunk

@@ -25,75 +25,9 @@ namespace xcg {
 
 constexpr uint32_t NO_SRC = ~0u;   // an empty table / window slot (never an offset: chunks are <= 1 MiB + 16)
 
+// The chunk's decoder in LDS (xcg_decode_ops.h), its sources chunk-local offsets.
 template <int XSLOTS>
-struct IndepDecWave {
-  uint64_t xk[XSLOTS];   // X keys (valid where xv != NO_SRC)
-  uint64_t wh[256];      // W hashes (valid where ws != NO_SRC)
-  uint32_t xv[XSLOTS];
-  uint32_t ws[256];
-};
-
-// One wave's LDS writes are visible to its own later reads, whichever lanes
-// made them (the LDS serves a wave's instructions in order): this only keeps
-// the compiler from moving or reusing LDS accesses across it.
-__device__ __forceinline__ void lds_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// X lookup, wave-uniform: the payload offset of h, or NO_SRC; `slot` is where h
-// is, or the empty slot it would take.  Lane l probes slot s + l.
-template <int XSLOTS>
-__device__ __forceinline__ uint32_t xtab_find(const IndepDecWave<XSLOTS>& S, uint64_t h, uint32_t& slot) {
-  const uint32_t l = (uint32_t)lane_id();
-  uint32_t s = tab_slot((uint32_t)h, (uint32_t)(h >> 32), XSLOTS - 1);
-  for (;;) {                                                 // ends: X is never more than half full
-    const uint32_t idx = (s + l) & (XSLOTS - 1);
-    const uint32_t v = S.xv[idx];
-    const uint64_t k = S.xk[idx];
-    const uint64_t hit = ballot(v != NO_SRC && k == h), emp = ballot(v == NO_SRC);
-    const uint32_t ph = hit ? (uint32_t)__builtin_ctzll(hit) : 64u, pe = emp ? (uint32_t)__builtin_ctzll(emp) : 64u;
-    if (ph < pe) {
-      slot = (s + ph) & (XSLOTS - 1);
-      return readlane(v, (int)ph);
-    }
-    if (pe < 64u) {
-      slot = (s + pe) & (XSLOTS - 1);
-      return NO_SRC;
-    }
-    s += 64u;
-  }
-}
-
-// XCodecWindow::declare (xcodec_window.h:68-99): the slot that holds the hash
-// already is emptied, the cursor's slot takes (hash, src), the cursor wraps.
-// Lane l owns slots l, l + 64, l + 128, l + 192.
-template <int XSLOTS>
-__device__ __forceinline__ void win_declare(IndepDecWave<XSLOTS>& S, uint32_t& cursor, uint64_t h, uint32_t src) {
-  const uint32_t l = (uint32_t)lane_id();
-#pragma unroll
-  for (uint32_t j = 0; j < 4; ++j) {
-    const uint32_t idx = l + 64u * j;
-    if (idx == cursor) {
-      S.wh[idx] = h;
-      S.ws[idx] = src;
-    } else if (S.ws[idx] != NO_SRC && S.wh[idx] == h) {
-      S.ws[idx] = NO_SRC;
-    }
-  }
-  cursor = (cursor + 1u) & 255u;
-  lds_wave_sync();
-}
-
-// Does an op start right at x[i] (an 0xF1 not followed by 0x00)?  Asked for the
-// next op before the current op's stores are issued: on gfx9 a load's wait
-// also drains the stores queued before it.
-__device__ __forceinline__ bool op_at(const uint8_t* x, uint32_t i, uint32_t len) {
-  if (i >= len) return false;
-  const uint32_t b0 = x[i], b1 = i + 1 < len ? (uint32_t)x[i + 1] : 0x100u;
-  return readfirst(b0) == MAGIC && readfirst(b1) != 0u;
-}
+using IndepDecWave = DecWave<XSLOTS, uint32_t>;
 
 template <int XSLOTS>
 __global__ __launch_bounds__(256) void decode_independent_kernel(XcgIndepDecodeArgs prm) {

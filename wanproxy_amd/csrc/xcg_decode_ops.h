@@ -1,9 +1,12 @@
 // Wave-level pieces of the XCodec op walk shared by the decode kernels
 // (xcg_decode.hip: one stream per batch; xcg_decode_indep.hip: one fresh
-// decoder per chunk): the op search, the literal-run copy, the EXTRACT payload
-// hash and the 2 KiB segment copy.  Device code only, one wave64 per call.
+// decoder per chunk; xcg_decode_group.hip: one per group of chunks): the op
+// search, the literal-run copy, the EXTRACT payload hash, the 2 KiB segment
+// copy, and the per-wave LDS decoder (cache table and window) of the
+// independent and grouped kernels.  Device code only, one wave64 per call.
 #pragma once
 #include "xcg_device.h"
+#include "xcg_cache.h"
 
 namespace xcg {
 
@@ -126,6 +129,90 @@ __device__ __forceinline__ uint64_t be64(P p) {
   uint64_t h = 0;
   for (int k = 0; k < 8; ++k) h = (h << 8) | p[k];
   return h;
+}
+
+// ---- a decoder in one wave's LDS (decode_independent_kernel, decode_group_kernel)
+//   X   its cache: hash -> where the EXTRACT payload lies (open addressing,
+//       probed 64 slots at a time); a later EXTRACT of a hash overwrites the
+//       value: cache_->replace, or the same bytes (xcodec_decoder.cc:106-136).
+//   W   its XCodecWindow (xcodec/xcodec_window.h:68-111): 256 slots of (hash,
+//       source) and the cursor.  A slot keeps the source its declare saw.
+// SRC names a payload: a chunk-local offset (uint32_t) or an offset into the
+// whole batch input (uint64_t).  ~0 is an empty slot, never an offset.
+template <int XSLOTS, typename SRC>
+struct DecWave {
+  static constexpr SRC NONE = (SRC)~(SRC)0;
+  uint64_t xk[XSLOTS];   // X keys (valid where xv != NONE)
+  uint64_t wh[256];      // W hashes (valid where ws != NONE)
+  SRC xv[XSLOTS];
+  SRC ws[256];
+};
+
+__device__ __forceinline__ uint32_t readlane_src(uint32_t v, int l) { return readlane(v, l); }
+__device__ __forceinline__ uint64_t readlane_src(uint64_t v, int l) { return readlane64(v, l); }
+
+// One wave's LDS writes are visible to its own later reads, whichever lanes
+// made them (the LDS serves a wave's instructions in order): this only keeps
+// the compiler from moving or reusing LDS accesses across it.
+__device__ __forceinline__ void lds_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// X lookup, wave-uniform: the payload source of h, or NONE; `slot` is where h
+// is, or the empty slot it would take.  Lane l probes slot s + l.
+template <int XSLOTS, typename SRC>
+__device__ __forceinline__ SRC xtab_find(const DecWave<XSLOTS, SRC>& S, uint64_t h, uint32_t& slot) {
+  constexpr SRC NONE = DecWave<XSLOTS, SRC>::NONE;
+  const uint32_t l = (uint32_t)lane_id();
+  uint32_t s = tab_slot((uint32_t)h, (uint32_t)(h >> 32), XSLOTS - 1);
+  for (;;) {                                                 // ends: X is never more than half full
+    const uint32_t idx = (s + l) & (XSLOTS - 1);
+    const SRC v = S.xv[idx];
+    const uint64_t k = S.xk[idx];
+    const uint64_t hit = ballot(v != NONE && k == h), emp = ballot(v == NONE);
+    const uint32_t ph = hit ? (uint32_t)__builtin_ctzll(hit) : 64u, pe = emp ? (uint32_t)__builtin_ctzll(emp) : 64u;
+    if (ph < pe) {
+      slot = (s + ph) & (XSLOTS - 1);
+      return readlane_src(v, (int)ph);
+    }
+    if (pe < 64u) {
+      slot = (s + pe) & (XSLOTS - 1);
+      return NONE;
+    }
+    s += 64u;
+  }
+}
+
+// XCodecWindow::declare (xcodec_window.h:68-99): the slot that holds the hash
+// already is emptied, the cursor's slot takes (hash, src), the cursor wraps.
+// Lane l owns slots l, l + 64, l + 128, l + 192.
+template <int XSLOTS, typename SRC>
+__device__ __forceinline__ void win_declare(DecWave<XSLOTS, SRC>& S, uint32_t& cursor, uint64_t h, SRC src) {
+  constexpr SRC NONE = DecWave<XSLOTS, SRC>::NONE;
+  const uint32_t l = (uint32_t)lane_id();
+#pragma unroll
+  for (uint32_t j = 0; j < 4; ++j) {
+    const uint32_t idx = l + 64u * j;
+    if (idx == cursor) {
+      S.wh[idx] = h;
+      S.ws[idx] = src;
+    } else if (S.ws[idx] != NONE && S.wh[idx] == h) {
+      S.ws[idx] = NONE;
+    }
+  }
+  cursor = (cursor + 1u) & 255u;
+  lds_wave_sync();
+}
+
+// Does an op start right at x[i] (an 0xF1 not followed by 0x00)?  Asked for the
+// next op before the current op's stores are issued: on gfx9 a load's wait
+// also drains the stores queued before it.
+__device__ __forceinline__ bool op_at(const uint8_t* x, uint32_t i, uint32_t len) {
+  if (i >= len) return false;
+  const uint32_t b0 = x[i], b1 = i + 1 < len ? (uint32_t)x[i + 1] : 0x100u;
+  return readfirst(b0) == MAGIC && readfirst(b1) != 0u;
 }
 
 }  // namespace xcg

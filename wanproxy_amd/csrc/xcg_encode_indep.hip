@@ -4,17 +4,6 @@
 
 namespace xcg {
 
-// INDEP_W chunk-waves per workgroup, INDEP_OCC workgroups per CU: four waves
-// per SIMD, one resident wave per chunk of a 4096-chunk launch.
-constexpr int INDEP_W = 4;
-constexpr int INDEP_OCC = 4;
-// The 64 KiB / 128 KiB instance's direct-mapped key table: 2 << 9 = 1024 slots
-// per wave.  The input ring's 4 KiB per wave came out of it (2048 slots before),
-// so a workgroup stays at 36,736 B and four share a CU's LDS; the smaller table
-// alone measured +0.4 %, the ring 0.942 of the register prefetch's time
-// (profiles/indep_ring_ab.txt).
-constexpr int INDEP_LOGNB = 9;
-
 template <int LOGNB, int MAXD>
 __global__ __launch_bounds__(64 * INDEP_W, INDEP_OCC) void encode_independent_kernel(EncParams prm) {
   __shared__ IndepLDS<LOGNB, MAXD, INDEP_W> S;

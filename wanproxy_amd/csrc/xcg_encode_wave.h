@@ -28,8 +28,9 @@
 // wave as they are resolved, into the chunk's output slot.
 //
 // This header is the device code the encoder's units share: encode_chunk and
-// its parts.  Its kernels: xcg_encode_indep.hip, xcg_encode_stream.h (instances
-// in xcg_encode_stream.hip and _lru.hip); xcg_encode_screen.hip uses the piece sums.
+// its parts.  Its kernels: xcg_encode_indep.hip, xcg_encode_group.hip,
+// xcg_encode_stream.h (instances in xcg_encode_stream.hip and _lru.hip);
+// xcg_encode_screen.hip uses the piece sums.
 #pragma once
 #include <stddef.h>
 
@@ -167,6 +168,18 @@ struct EncParams {
   // ---- (stream) parse only the chunks of a work list: work[0] = count, work[1..] chunks (null: all)
   const uint32_t* work;
 };
+
+// INDEP_W chunk-waves per workgroup, INDEP_OCC workgroups per CU: four waves
+// per SIMD, one resident wave per chunk of a 4096-chunk launch.
+// (xcg_encode_indep.hip, and one wave per group in xcg_encode_group.hip)
+constexpr int INDEP_W = 4;
+constexpr int INDEP_OCC = 4;
+// The 64 KiB / 128 KiB instance's direct-mapped key table: 2 << 9 = 1024 slots
+// per wave.  The input ring's 4 KiB per wave came out of it (2048 slots before),
+// so a workgroup stays at 36,736 B and four share a CU's LDS; the smaller table
+// alone measured +0.4 %, the ring 0.942 of the register prefetch's time
+// (profiles/indep_ring_ab.txt).
+constexpr int INDEP_LOGNB = 9;
 
 // ------------------------------------------------------------------ emission
 
@@ -744,18 +757,36 @@ struct GlbView {
   uint32_t* rsv;  // (stream) the wave's restart state, LDS: slot, old nev, nhits, olen, ndecl, restart ndecl
 };
 
-template <int LOGNB, int MAXD, bool STREAM, bool LRU = false>
+// GROUP (xcg_encode_group.hip): the chunk is one encode() call of a short
+// stream whose earlier calls this wave has made, on the same cache.  The key
+// table, the records and the overflow keys are then carried, not cleared
+// (the kernel clears them once per group), with their counts in `gc`; a record
+// names its segment by its byte offset in the whole batch input (T.rc the low
+// word, gc->rch bits 32..47: device addresses have 48 bits), since it may lie
+// in an earlier chunk, placed anywhere.  Everything else of the parse is per
+// call, as in the reference.
+struct GroupCarry {
+  uint32_t ndecl, novf;   // records and overflow keys so far
+  uint16_t* rch;          // LDS, [MAXD]: bits 32..47 of the records' input offsets
+  int done, total;        // bytes of the group parsed before this chunk, and in all (progress_priority)
+};
+
+template <int LOGNB, int MAXD, bool STREAM, bool LRU = false, bool GROUP = false>
 __device__ __forceinline__ void encode_chunk(const EncParams& prm, char* kblk, const uint32_t kofs,
                                              WaveRecs<LOGNB, MAXD, (!STREAM && MAXD <= 72)>& T, const uint32_t chunk,
-                                             const GlbView gs, const lds_u8* ring = nullptr) {
+                                             const GlbView gs, const lds_u8* ring = nullptr,
+                                             GroupCarry* gc = nullptr) {
+  static_assert(!GROUP || (!STREAM && !LRU), "a group is a batch of fresh caches");
   constexpr int NB = 1 << LOGNB;
   // independent chunks of up to 128 KiB: direct-mapped NX2 keys (roll_probe_dm), input through `ring`
   constexpr bool DM = !STREAM && MAXD <= 72;
   const int l = lane_id();
 
-  const uint8_t* x = prm.in + prm.chunk_off[chunk];
-  const int L = (int)prm.chunk_len[chunk];
-  uint8_t* const out = prm.out + prm.out_off[chunk];
+  // (GROUP: a later chunk's loads follow the kernel's own stores, so they are
+  // vector loads; their values are wave-uniform, and the parse state stays in SGPRs)
+  const uint8_t* x = prm.in + (GROUP ? readfirst64(prm.chunk_off[chunk]) : prm.chunk_off[chunk]);
+  const int L = (int)(GROUP ? readfirst(prm.chunk_len[chunk]) : prm.chunk_len[chunk]);
+  uint8_t* const out = prm.out + (GROUP ? readfirst64(prm.out_off[chunk]) : prm.out_off[chunk]);
   const bool oob = (prm.flags & XCG_FLAG_OOB) != 0;
   const bool nullcache = (prm.flags & XCG_FLAG_NULLCACHE) != 0;
   uint32_t olen = 0;
@@ -764,7 +795,8 @@ __device__ __forceinline__ void encode_chunk(const EncParams& prm, char* kblk, c
   WaveClock clk;
   // A chunk longer than the launch's bound would overrun the records sized
   // for it: refuse it loudly (status bit 3) instead.
-  if ((uint32_t)L > prm.max_len || (uint32_t)L / SEG >= (uint32_t)MAXD) {
+  // (a group is refused as a whole by its kernel, which has summed its lengths)
+  if (!GROUP && ((uint32_t)L > prm.max_len || (uint32_t)L / SEG >= (uint32_t)MAXD)) {
     if (l == 0) {
       prm.out_len[chunk] = 0;
       if (prm.status) atomicOr(prm.status, 8);
@@ -777,13 +809,30 @@ __device__ __forceinline__ void encode_chunk(const EncParams& prm, char* kblk, c
     if (l == 0) {
       prm.out_len[chunk] = olen;
       if (LRU) prm.nev[chunk] = 0;                 // (no cache reference; the list is scratch)
+      if constexpr (GROUP) {                       // (the carried cache is untouched: ordinary traffic)
+        if (prm.stats) {
+          for (int k = 0; k < 4; ++k) prm.stats[4 * chunk + k] = 0u;
+        }
+      }
     }
+    // (GROUP: lane 0's branch joins here, not at the group loop's latch, where
+    // the carried counts of the different exits meet: they stay wave-uniform)
+    if constexpr (GROUP) __builtin_amdgcn_wave_barrier();
     return;
   }
 
   uint32_t* const keyt = (uint32_t*)(kblk + kofs);
-  for (int k = l; k < 2 * NB; k += 64) keyt[k] = DM ? dm_empty<LOGNB>((uint32_t)k) : kempty<LOGNB>((uint32_t)k >> 1);
+  if constexpr (!GROUP) {
+    for (int k = l; k < 2 * NB; k += 64) keyt[k] = DM ? dm_empty<LOGNB>((uint32_t)k) : kempty<LOGNB>((uint32_t)k >> 1);
+  }
   uint32_t ndecl = 0, novf = 0;
+  if constexpr (GROUP) { ndecl = gc->ndecl; novf = gc->novf; }
+  // (GROUP) a record's segment: its offset in the batch input; else in the chunk
+  const uint64_t xin = GROUP ? (uint64_t)(x - prm.in) : 0u;
+  auto rec_bytes = [&](uint32_t d) -> const uint8_t* {
+    if constexpr (GROUP) return prm.in + (((uint64_t)readfirst((uint32_t)gc->rch[d]) << 32) | readfirst(T.rc[d]));
+    else return x + readfirst(T.rc[d]);
+  };
   // (stream) the own key table overflowed: this parse may have missed one of
   // its own declarations.  The chunk's hit count becomes maxh + 1, which the
   // verification treats as "always re-parse" (structured data can put a
@@ -835,7 +884,9 @@ __device__ __forceinline__ void encode_chunk(const EncParams& prm, char* kblk, c
   auto insert_dm = [&](uint32_t lo, uint32_t hi, uint32_t c, uint32_t k2, uint32_t sl, uint32_t s0) {
     const uint32_t d = ndecl++, ke = dm_empty<LOGNB>(sl);
     if (l == 0) {
-      T.rlo[d] = lo; T.rhi[d] = hi; T.rc[d] = c;
+      T.rlo[d] = lo; T.rhi[d] = hi;
+      if constexpr (GROUP) { T.rc[d] = (uint32_t)(xin + c); gc->rch[d] = (uint16_t)((xin + c) >> 32); }
+      else T.rc[d] = c;
       if (s0 == ke) keyt[sl] = k2;
       else if (novf < (uint32_t)ovf_cap<MAXD, DM>()) T.ovf_k[novf] = k2;
     }
@@ -856,7 +907,9 @@ __device__ __forceinline__ void encode_chunk(const EncParams& prm, char* kblk, c
     const uint32_t b = kbucket<LOGNB>(k), ke = kempty<LOGNB>(b);
     const uint32_t s0 = readfirst(keyt[2 * b]), s1 = readfirst(keyt[2 * b + 1]);
     if (l == 0) {
-      T.rlo[d] = lo; T.rhi[d] = hi; T.rc[d] = c;
+      T.rlo[d] = lo; T.rhi[d] = hi;
+      if constexpr (GROUP) { T.rc[d] = (uint32_t)(xin + c); gc->rch[d] = (uint16_t)((xin + c) >> 32); }
+      else T.rc[d] = c;
       if (s0 == ke) keyt[2 * b] = k;
       else if (s1 == ke) keyt[2 * b + 1] = k;
       else if (novf < (uint32_t)ovf_cap<MAXD>()) T.ovf_k[novf] = k;
@@ -1196,7 +1249,8 @@ __device__ __forceinline__ void encode_chunk(const EncParams& prm, char* kblk, c
     const int q0 = p + 32 * l;
     const bool contig = (p == p_prev + SEG);
     ++n_pieces;
-    progress_priority(s, L);
+    if constexpr (GROUP) progress_priority(gc->done + s, gc->total);   // the wave's whole job: its group
+    else progress_priority(s, L);
     // vmcnt counts loads and stores together, in order (gfx9): every wait on
     // a load also waits for all older stores.  So fresh loads are waited for
     // here, inside their branch, and the prefetch below is waited for after
@@ -1531,7 +1585,7 @@ __device__ __forceinline__ void encode_chunk(const EncParams& prm, char* kblk, c
             hh.y = readfirst(lane_window_hi(P, (s - p) >> 5));
             hh.z = DM ? readlane(NX2, (s - p) >> 5) : 0u;
           } else {
-            hh = window_hash_u(fill >= 0 ? x + readfirst(T.rc[fill]) : x + s);
+            hh = window_hash_u(fill >= 0 ? rec_bytes((uint32_t)fill) : x + s);
           }
           if (fill >= 0) {
             if (l == 0) T.rhi[fill] = hh.y;
@@ -1546,7 +1600,7 @@ __device__ __forceinline__ void encode_chunk(const EncParams& prm, char* kblk, c
         }
         // Where the hash is declared: this chunk (d), the persistent cache, or
         // an earlier chunk of the batch.  src = that segment's bytes.
-        const uint8_t* src = d >= 0 ? x + readfirst(T.rc[d]) : nullptr;
+        const uint8_t* src = d >= 0 ? rec_bytes((uint32_t)d) : nullptr;
         if (LRU && d >= 0) record(lo, hi, 2u * (uint32_t)s + 1u, EV_HIT, 0u);
         // (through the lane filter first: the forced events of a chunk's last
         // one or two windows and own-table false positives have not passed it)
@@ -1607,6 +1661,7 @@ __device__ __forceinline__ void encode_chunk(const EncParams& prm, char* kblk, c
     if (have_cand) declare(last + 1);                         // :257-261 (after every lookup)
     if (base < L) olen += escape_u(out + olen, x, (uint32_t)base, (uint32_t)L);   // :267-269
   }
+  if constexpr (GROUP) { gc->ndecl = ndecl; gc->novf = novf; }   // (every candidate is declared by now)
   if (STREAM) {
     // This round's declarations; flag a change against the previous round's.
     const uint32_t nold = prm.ndecl[chunk];
@@ -1640,6 +1695,7 @@ __device__ __forceinline__ void encode_chunk(const EncParams& prm, char* kblk, c
       }
     }
   }
+  if constexpr (GROUP) __builtin_amdgcn_wave_barrier();   // (as at the early exit)
 }
 
 }  // namespace xcg

@@ -124,6 +124,12 @@ def lib():
     L.xcg_decode_batch_independent.argtypes = [vp, u8p, u64p, u32p, C.c_uint32, C.c_uint32, u8p, u64p, u64p, u64p, vp,
                                                u64p, u64p, vp]
     L.xcg_decode_batch_independent.restype = C.c_int
+    L.xcg_encode_batch_grouped.argtypes = [vp, u8p, u64p, u32p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, u8p, u64p,
+                                           u64p, u32p, vp]
+    L.xcg_encode_batch_grouped.restype = C.c_int
+    L.xcg_decode_batch_grouped.argtypes = [vp, u8p, u64p, u32p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, u8p, u64p,
+                                           u64p, u64p, vp, u64p, u64p, vp]
+    L.xcg_decode_batch_grouped.restype = C.c_int
     L.xcg_window_create.argtypes = [vp, C.POINTER(C.c_void_p)]
     L.xcg_window_create.restype = C.c_int
     L.xcg_window_destroy.argtypes = [vp]
@@ -524,6 +530,139 @@ class Context:
             caps[todo[again]] = ol[again]
             todo = todo[again]
         return outs, st, cons, unk
+
+    # ------------------------------------------------- grouped (short streams)
+    def encode_batch_grouped_device(self, d_in, d_off, d_len, n, d_group_first, n_groups, max_group_len, d_out,
+                                    d_out_off, d_out_len, d_stats=None, stream=None):
+        """Raw launch of xcg_encode_batch_grouped on device tensors (all torch
+        tensors on this device); asynchronous on `stream`."""
+        _check(lib().xcg_encode_batch_grouped(
+            self.h, C.c_void_p(d_in.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(d_len.data_ptr()), int(n),
+            C.c_void_p(d_group_first.data_ptr()), int(n_groups), int(max_group_len), C.c_void_p(d_out.data_ptr()),
+            C.c_void_p(d_out_off.data_ptr()), C.c_void_p(d_out_len.data_ptr()),
+            C.c_void_p(d_stats.data_ptr()) if d_stats is not None else None, _stream_ptr(stream)))
+
+    def decode_batch_grouped_device(self, d_enc, d_off, d_len, n, d_group_first, n_groups, max_group_len, d_out,
+                                    d_out_off, d_out_cap, d_out_len, d_status, d_consumed, d_first_unknown=None,
+                                    stream=None):
+        """Raw launch of xcg_decode_batch_grouped on device tensors; asynchronous
+        on `stream`."""
+        _check(lib().xcg_decode_batch_grouped(
+            self.h, C.c_void_p(d_enc.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(d_len.data_ptr()), int(n),
+            C.c_void_p(d_group_first.data_ptr()), int(n_groups), int(max_group_len), C.c_void_p(d_out.data_ptr()),
+            C.c_void_p(d_out_off.data_ptr()), C.c_void_p(d_out_cap.data_ptr()), C.c_void_p(d_out_len.data_ptr()),
+            C.c_void_p(d_status.data_ptr()), C.c_void_p(d_consumed.data_ptr()),
+            C.c_void_p(d_first_unknown.data_ptr()) if d_first_unknown is not None else None, _stream_ptr(stream)))
+
+    def encode_groups(self, data, offs, lens, group_first, with_stats=False, max_group_len=None, check=True):
+        """Encode chunks of host `data` as many short streams: group g is the
+        chunks [group_first[g], group_first[g + 1]), successive encode() calls on
+        one fresh cache of its own (xcg_encode_batch_grouped).  Returns one
+        encoding per chunk (and the per-chunk stats if asked).  max_group_len
+        defaults to the largest group's total; check=False leaves the context's
+        status word to the caller (a refused group then shows as empty outputs)."""
+        import torch
+        dev = torch.device('cuda', self.device)
+        a = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        gf = np.ascontiguousarray(group_first, dtype=np.uint32)
+        n, ng = int(offs.size), int(gf.size) - 1
+        if n == 0 or ng <= 0:
+            return ([b''] * n, np.zeros((n, 4), np.uint32)) if with_stats else [b''] * n
+        if max_group_len is None:
+            cs = np.concatenate([[0], np.cumsum(lens.astype(np.uint64))]).astype(np.uint64)
+            g0, g1 = np.minimum(gf[:-1], n), np.minimum(gf[1:], n)
+            max_group_len = int(max(0, (cs[g1].astype(np.int64) - cs[g0].astype(np.int64)).max()))
+        bounds = 2 * lens.astype(np.uint64) + 16
+        oo = np.zeros(n, dtype=np.uint64)
+        oo[1:] = np.cumsum(bounds)[:-1]
+        d_in = torch.from_numpy(a.copy() if a.size else np.zeros(1, np.uint8)).to(dev)
+        d_off = torch.from_numpy(offs.view(np.int64)).to(dev)
+        d_len = torch.from_numpy(lens.view(np.int32)).to(dev)
+        d_gf = torch.from_numpy(gf.view(np.int32)).to(dev)
+        d_oo = torch.from_numpy(oo.view(np.int64)).to(dev)
+        d_out = torch.zeros(int(bounds.sum()), dtype=torch.uint8, device=dev)
+        d_ol = torch.zeros(n, dtype=torch.int64, device=dev)
+        d_st = torch.zeros(4 * n, dtype=torch.int32, device=dev)
+        self.encode_batch_grouped_device(d_in, d_off, d_len, n, d_gf, ng, max_group_len, d_out, d_oo, d_ol, d_st)
+        torch.cuda.synchronize(dev)
+        if check:
+            self.status()
+        out = d_out.cpu().numpy()
+        ol = d_ol.cpu().numpy().astype(np.uint64)
+        res = [out[int(oo[i]):int(oo[i] + ol[i])].tobytes() for i in range(n)]
+        if with_stats:
+            return res, d_st.cpu().numpy().view(np.uint32).reshape(n, 4)
+        return res
+
+    def decode_groups(self, groups, out_caps=None, max_group_len=None, check=True):
+        """Decode many short streams: groups[g] is the list of one stream's
+        encoded chunks, decoded in order on one fresh decoder of its own
+        (xcg_decode_batch_grouped).  out_caps: per-chunk slot sizes, flat in
+        chunk order (default len * 205 + 4096); the groups that hold a chunk
+        whose slot was too small are run once more with the sizes the kernel
+        reported.  Returns, flat in chunk order, a list of (status, out,
+        consumed, first_unknown)."""
+        import torch
+        dev = torch.device('cuda', self.device)
+        encs = [e for grp in groups for e in grp]
+        n = len(encs)
+        gsz = np.array([len(grp) for grp in groups], dtype=np.int64)
+        gfirst = np.concatenate([[0], np.cumsum(gsz)]).astype(np.int64)
+        st = np.zeros(n, dtype=np.int32)
+        cons = np.zeros(n, dtype=np.uint64)
+        unk = np.zeros(n, dtype=np.uint64)
+        outs = [b''] * n
+        if n == 0:
+            return []
+        caps = (np.array([len(e) * 205 + 4096 for e in encs], dtype=np.uint64) if out_caps is None
+                else np.ascontiguousarray(out_caps, dtype=np.uint64).copy())
+        todo_g = np.arange(len(groups))
+        for attempt in range(2):
+            idx = np.concatenate([np.arange(gfirst[g], gfirst[g + 1]) for g in todo_g]).astype(np.int64)
+            m = int(idx.size)
+            if m == 0:
+                break
+            sub = [encs[i] for i in idx]
+            lens = np.array([len(e) for e in sub], dtype=np.uint32)
+            offs = np.zeros(m, dtype=np.uint64)
+            offs[1:] = np.cumsum(lens.astype(np.uint64))[:-1]
+            gf = np.concatenate([[0], np.cumsum(gsz[todo_g])]).astype(np.uint32)
+            cs = np.concatenate([[0], np.cumsum(lens.astype(np.uint64))]).astype(np.int64)
+            mgl = int((cs[gf[1:]] - cs[gf[:-1]]).max()) if max_group_len is None else int(max_group_len)
+            oo = np.zeros(m, dtype=np.uint64)
+            oo[1:] = np.cumsum(caps[idx])[:-1]
+            d_in = torch.from_numpy(np.frombuffer(b''.join(sub) or b'\0', dtype=np.uint8).copy()).to(dev)
+            d_off = torch.from_numpy(offs.view(np.int64)).to(dev)
+            d_len = torch.from_numpy(lens.view(np.int32)).to(dev)
+            d_gf = torch.from_numpy(gf.view(np.int32)).to(dev)
+            d_oo = torch.from_numpy(oo.view(np.int64)).to(dev)
+            d_cap = torch.from_numpy(caps[idx].view(np.int64)).to(dev)
+            d_out = torch.zeros(max(int(caps[idx].sum()), 1), dtype=torch.uint8, device=dev)
+            d_ol = torch.zeros(m, dtype=torch.int64, device=dev)
+            d_st = torch.zeros(m, dtype=torch.int32, device=dev)
+            d_cons = torch.zeros(m, dtype=torch.int64, device=dev)
+            d_unk = torch.zeros(m, dtype=torch.int64, device=dev)
+            self.decode_batch_grouped_device(d_in, d_off, d_len, m, d_gf, int(gf.size) - 1, mgl, d_out, d_oo, d_cap,
+                                             d_ol, d_st, d_cons, d_unk)
+            torch.cuda.synchronize(dev)
+            if check:
+                self.status()
+            out = d_out.cpu().numpy()
+            ol = d_ol.cpu().numpy().view(np.uint64)
+            st[idx] = d_st.cpu().numpy()
+            cons[idx] = d_cons.cpu().numpy().view(np.uint64)
+            unk[idx] = d_unk.cpu().numpy().view(np.uint64)
+            for k, i in enumerate(idx):
+                outs[i] = b'' if st[i] == XCG_CHUNK_NOROOM else out[int(oo[k]):int(oo[k]) + int(ol[k])].tobytes()
+            again = st[idx] == XCG_CHUNK_NOROOM
+            if attempt or not again.any():
+                break
+            caps[idx[again]] = ol[again]
+            chunk_group = np.searchsorted(gfirst, idx[again], side='right') - 1
+            todo_g = np.unique(chunk_group)
+        return [(int(st[i]), outs[i], int(cons[i]), int(unk[i])) for i in range(n)]
 
     def decode_call(self, data: bytes, out_cap: int = None):
         """One XCodecDecoder::decode(output, input, unknown) call from host memory
