@@ -234,6 +234,50 @@ int xcg_last_rounds(xcg_ctx *ctx);
  * segment's XCodecHash (XCG_EINVAL otherwise). */
 int xcg_cache_lookup_host(xcg_ctx *ctx, uint64_t hash, uint8_t *seg_out);
 int xcg_cache_enter_host(xcg_ctx *ctx, uint64_t hash, const uint8_t *seg);
+/* Bulk learn: warm a memory cache with n segments in one pass.  Segment i is
+ * d_segs[2048 i .. 2048 i + 2048) (any alignment), and the call equals n calls
+ * xcg_cache_enter_host(ctx, XCodecHash(segment i), segment i) in order --
+ * <LEARN>'s lookup, then nothing (equal bytes), replace (other bytes) or enter
+ * (absent), xcodec/xcodec_pipe_pair.cc:311-327 -- with the hashes computed on
+ * the device; d_hash[i] (nullable) receives segment i's hash in host byte
+ * order, so a host mirror of the cache needs no hashing.  The context's flags
+ * matter as little as they do to xcg_cache_enter_host.
+ *   Unbounded cache: it ends up with what it held plus every distinct hash of
+ *   the batch, each with the bytes of its last occurrence.  If that is more
+ *   than the capacity: XCG_EOVERFLOW and the cache is exactly as it was (all
+ *   or nothing).  Synchronises `stream` once.
+ *   Bounded cache: every occurrence is a reference at its position (a hit
+ *   refreshes, a miss enters and evicts at the limit), so it ends up with the
+ *   `limit` most recently referenced distinct hashes of its earlier content
+ *   and the batch, in the order of their last reference; n may exceed the
+ *   limit any number of times.  Asynchronous on `stream` (no synchronisation),
+ *   and later encode and decode batches continue the same LRU clock.
+ * The BACKREF window, xcg_last_declarations and xcg_last_references are not
+ * touched.  The call is ordered behind the context's earlier work and ahead of
+ * its later work on any stream.  n == 0 is XCG_OK; n > 2^30 is XCG_EINVAL.
+ * XCG_ENOTSUP on a pair context, with nothing changed: the volume file is a
+ * pair's persistence (xcg_disk_save) and xcg_cache_enter_host its learn.
+ * Temporaries are stream-ordered and gone when the call's work is done.
+ * xcg_cache_learn_host: the same from host memory (copies in, learns on the
+ * default stream, copies the hashes out; synchronous). */
+int xcg_cache_learn_batch(xcg_ctx *ctx, const uint8_t *d_segs, uint64_t n, uint64_t *d_hash, void *stream);
+int xcg_cache_learn_host(xcg_ctx *ctx, const uint8_t *h_segs, uint64_t n, uint64_t *h_hash);
+/* Export: every live (hash, segment) of a memory cache, in a fixed order, with
+ * nothing changed (no LRU entry is refreshed) -- what `tack -p` saves
+ * (programs/tack/tack.cc:103-127).  Bounded cache: least recently used first;
+ * unbounded: ascending hash, so equal caches export byte-identical snapshots.
+ * Segment j goes to d_segs[2048 j ..) (any alignment), its hash in host byte
+ * order to d_hash[j] (nullable).  *h_count receives the number of segments;
+ * if it exceeds cap_segments: XCG_EOVERFLOW, *h_count still the number needed,
+ * nothing written.  Waits for the context's earlier work (the count is read
+ * back), then asynchronous on `stream`.  Learning an export, in its order,
+ * into a fresh context of the same kind and limit reproduces the cache: its
+ * later behaviour and its export are the same.  XCG_ENOTSUP on a pair context.
+ * xcg_cache_export_host: the same into host memory (synchronous). */
+int xcg_cache_export(xcg_ctx *ctx, uint8_t *d_segs, uint64_t *d_hash, uint64_t cap_segments, uint64_t *h_count,
+                     void *stream);
+int xcg_cache_export_host(xcg_ctx *ctx, uint8_t *h_segs, uint64_t *h_hash, uint64_t cap_segments,
+                          uint64_t *h_count);
 /* Declarations (hash, position in the chunk) chunk `chunk` of the last
  * XCG_SEM_STREAM batch made, in order: what XCodecEncoder::encode_declaration
  * entered into the cache (xcodec/xcodec_encoder.cc:276-313).  On a bounded

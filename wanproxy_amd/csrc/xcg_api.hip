@@ -1007,6 +1007,89 @@ int xcg_cache_enter_host(xcg_ctx* c, uint64_t hash, const uint8_t* seg) {
   return res == -2 ? XCG_EOVERFLOW : XCG_OK;
 }
 
+// Bulk learn / export of a memory cache (xcg_cache_bulk.hip): n <LEARN>
+// sequences in one pass, and every live (hash, segment) in a fixed order.
+int xcg_cache_learn_batch(xcg_ctx* c, const uint8_t* d_segs, uint64_t n, uint64_t* d_hash, void* stream) {
+  if (!c || (n && !d_segs) || n > (1ull << 30)) return XCG_EINVAL;
+  if (c->pair) return XCG_ENOTSUP;
+  if (n == 0) return XCG_OK;
+  DeviceGuard g(c->device);
+  int rc = ensure_cache(c);
+  if (rc != XCG_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  ctx_order(c, st);
+  XcgBulkLearn a{};
+  a.segs = d_segs;
+  a.n = n;
+  a.hash_out = d_hash;
+  a.g = c->g;
+  a.lru = c->bounded ? &c->lru : nullptr;
+  a.status = c->d_status;
+  rc = xcg_bulk_learn(&a, st);
+  ctx_mark(c, st);
+  return rc == -12 ? XCG_ENOMEM : status_of(rc);
+}
+
+int xcg_cache_learn_host(xcg_ctx* c, const uint8_t* h_segs, uint64_t n, uint64_t* h_hash) {
+  if (!c || (n && !h_segs) || n > (1ull << 30)) return XCG_EINVAL;
+  if (c->pair) return XCG_ENOTSUP;
+  if (n == 0) return XCG_OK;
+  DeviceGuard g(c->device);
+  xcg::DevMem mem;                   // (freed when the call returns)
+  uint8_t* d_segs = nullptr;
+  uint64_t* d_hash = nullptr;
+  if (!(mem.dev(&d_segs, n * XCG_SEGMENT_LENGTH) && (!h_hash || mem.dev(&d_hash, 8 * n)))) return XCG_ENOMEM;
+  if (hipMemcpy(d_segs, h_segs, n * XCG_SEGMENT_LENGTH, hipMemcpyHostToDevice) != hipSuccess) return XCG_EHIP;
+  const int rc = xcg_cache_learn_batch(c, d_segs, n, d_hash, nullptr);
+  // (the copy back, or the wait alone, also keeps d_segs alive until the pass has read it)
+  if (h_hash ? hipMemcpy(h_hash, d_hash, 8 * n, hipMemcpyDeviceToHost) != hipSuccess
+             : hipStreamSynchronize(nullptr) != hipSuccess)
+    return rc != XCG_OK ? rc : XCG_EHIP;
+  return rc;
+}
+
+int xcg_cache_export(xcg_ctx* c, uint8_t* d_segs, uint64_t* d_hash, uint64_t cap_segments, uint64_t* h_count,
+                     void* stream) {
+  if (!c || !h_count) return XCG_EINVAL;
+  if (c->pair) return XCG_ENOTSUP;
+  *h_count = 0;
+  if (!c->g.keys) return XCG_OK;
+  DeviceGuard g(c->device);
+  uint32_t live = 0;
+  if (ctx_wait(c) != XCG_OK || hipMemcpy(&live, c->g.nseg, 4, hipMemcpyDeviceToHost) != hipSuccess) return XCG_EHIP;
+  if (live > c->g.seg_cap) live = c->g.seg_cap;
+  *h_count = live;
+  if (live > cap_segments) return XCG_EOVERFLOW;
+  if (live == 0) return XCG_OK;
+  if (!d_segs) return XCG_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  ctx_order(c, st);
+  const int rc = xcg_bulk_export(&c->g, c->bounded ? &c->lru : nullptr, live, d_segs, d_hash, st);
+  ctx_mark(c, st);
+  return rc == -12 ? XCG_ENOMEM : status_of(rc);
+}
+
+int xcg_cache_export_host(xcg_ctx* c, uint8_t* h_segs, uint64_t* h_hash, uint64_t cap_segments, uint64_t* h_count) {
+  if (!c || !h_count) return XCG_EINVAL;
+  if (c->pair) return XCG_ENOTSUP;
+  const uint64_t live = xcg_cache_size(c);
+  *h_count = live;
+  if (live > cap_segments) return XCG_EOVERFLOW;
+  if (live == 0) return XCG_OK;
+  if (!h_segs) return XCG_EINVAL;
+  DeviceGuard g(c->device);
+  xcg::DevMem mem;                   // (freed when the call returns)
+  uint8_t* d_segs = nullptr;
+  uint64_t* d_hash = nullptr;
+  if (!(mem.dev(&d_segs, live * XCG_SEGMENT_LENGTH) && mem.dev(&d_hash, 8 * live))) return XCG_ENOMEM;
+  const int rc = xcg_cache_export(c, d_segs, d_hash, live, h_count, nullptr);
+  if (rc != XCG_OK) return rc;
+  if (hipMemcpy(h_segs, d_segs, live * XCG_SEGMENT_LENGTH, hipMemcpyDeviceToHost) != hipSuccess ||
+      (h_hash && hipMemcpy(h_hash, d_hash, 8 * live, hipMemcpyDeviceToHost) != hipSuccess))
+    return XCG_EHIP;
+  return XCG_OK;
+}
+
 int xcg_last_declarations(xcg_ctx* c, uint32_t chunk, uint64_t* h_hash, uint32_t* h_pos, uint32_t cap,
                           uint32_t* h_count) {
   if (!c || !h_count || !c->bs.decl) return XCG_EINVAL;

@@ -316,6 +316,7 @@ extern "C" int xcg_lru_encode_stream(const XcgStreamArgs* a, XcgLruState* L, int
 extern "C" int xcg_lru_times(const LruBatch* b, XcgLruState* L, hipStream_t st);
 extern "C" int xcg_lru_commit(const LruBatch* b, XcgLruState* L, hipStream_t st);
 extern "C" int xcg_lru_reset_times(XcgLruState* L, hipStream_t st);
+extern "C" int xcg_lru_rebuild_table(const XcgCacheView* g, XcgLruState* L, int32_t* status, hipStream_t st);
 extern "C" int xcg_launch_seed_tiling(const XcgStreamArgs* a, hipStream_t stream);
 extern "C" int xcg_launch_encode_independent(const uint8_t* d_in, const uint64_t* d_chunk_off,
                                              const uint32_t* d_chunk_len, uint32_t n, uint32_t max_chunk_len,
@@ -349,6 +350,20 @@ extern "C" int xcg_launch_cache_lookup(const XcgCacheView* g, uint64_t key, uint
                                        hipStream_t s);
 extern "C" int xcg_launch_cache_enter(const XcgCacheView* g, uint64_t key, const uint8_t* seg, int replace_only,
                                       int32_t* result, hipStream_t s);
+// Bulk learn / export of a memory cache (xcg_cache_bulk.hip).  segs: n segments
+// back to back, any alignment; hash_out (nullable): each one's XCodecHash;
+// lru: the bounded cache's state, null on an unbounded one.
+struct XcgBulkLearn {
+  const uint8_t* segs;
+  uint64_t n;             // at most 2^30
+  uint64_t* hash_out;
+  XcgCacheView g;
+  XcgLruState* lru;
+  int32_t* status;
+};
+extern "C" int xcg_bulk_learn(const XcgBulkLearn* a, hipStream_t st);
+extern "C" int xcg_bulk_export(const XcgCacheView* g, const XcgLruState* lru, uint32_t live, uint8_t* d_segs,
+                               uint64_t* d_hash, hipStream_t st);
 extern "C" int xcg_launch_pack(const uint8_t* src, const uint64_t* src_off, const uint64_t* len, uint32_t n,
                                uint8_t* dst, uint64_t* dst_off, uint64_t* d_total, hipStream_t stream);
 extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, uint64_t* block_pos_out,

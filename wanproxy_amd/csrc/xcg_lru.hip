@@ -710,6 +710,19 @@ extern "C" int xcg_lru_commit(const LruBatch* bp, XcgLruState* L, hipStream_t st
 // decoder's: fixed by the stream).  h_tot: totals.  Synchronises.
 extern "C" int xcg_lru_times(const LruBatch* b, XcgLruState* L, hipStream_t st) { return lru_times(*b, L, false, st); }
 
+// G and its filters again from the live slots (alive, skey), as a commit does:
+// for a pass that decided the live set itself (xcg_cache_bulk.hip).
+extern "C" int xcg_lru_rebuild_table(const XcgCacheView* gv, XcgLruState* L, int32_t* status, hipStream_t st) {
+  using namespace xcg;
+  const HashTab g = tab_of(*gv);
+  const FiltSet fs = filters_of(*gv);
+  Wipe w{g, fs.filt, (u32x4*)fs.ftab, fs.fmask + 1, fs.gfilt, fs.gmask + 1};
+  hipLaunchKernelGGL(lru_wipe_kernel, dim3(1024), dim3(256), 0, st, w, (const uint32_t*)nullptr);
+  hipLaunchKernelGGL(lru_insert_alive_kernel, dim3(grid_for(L->C)), dim3(256), 0, st, L->C, (const uint32_t*)L->alive,
+                     (const uint64_t*)L->skey, g, fs, status, (const uint32_t*)nullptr);
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
 extern "C" int xcg_lru_reset_times(XcgLruState* L, hipStream_t st) {
   using namespace xcg;
   const unsigned cg = grid_for(L->C) < 1024 ? grid_for(L->C) : 1024;

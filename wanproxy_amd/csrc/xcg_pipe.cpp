@@ -226,13 +226,23 @@ int xcg_pipe::decode_ops() {
       const uint32_t count = (uint32_t)get_be(b + 1, 2);
       if (count == 0 || count > ASK_MAX) { rc = XCG_EPROTO; break; }
       if (avail < 3 + (size_t)SEG * count) break;
-      for (uint32_t k = 0; k < count; ++k) {
-        const uint8_t* seg = b + 3 + (size_t)SEG * k;
+      // The segments up to the first gratuitous one are learned -- lookup: equal
+      // -> redundant; else replace / enter (:311-327) -- in one batched call; a
+      // pair learns segment by segment (its disk level, xcg_cache_enter_host).
+      const bool pair = xcg_pair_xuid(dec) >= 0;
+      uint32_t accepted = 0;
+      for (; accepted < count; ++accepted) {
+        const uint8_t* seg = b + 3 + (size_t)SEG * accepted;
         const uint64_t h = seg_hash(seg);
         if (!unknown.erase(h)) { rc = XCG_EPROTO; break; }           // gratuitous <LEARN>
-        // lookup: equal -> redundant; else replace / enter (:311-327)
-        const int e = xcg_cache_enter_host(dec, h, seg);
-        if (e != XCG_OK) { rc = e; break; }
+        if (pair) {
+          const int e = xcg_cache_enter_host(dec, h, seg);
+          if (e != XCG_OK) { rc = e; break; }
+        }
+      }
+      if (!pair && accepted) {
+        const int e = xcg_cache_learn_host(dec, b + 3, accepted, nullptr);
+        if (e != XCG_OK) rc = e;
       }
       if (rc != XCG_OK) break;
       i += 3 + (size_t)SEG * count;

@@ -109,6 +109,14 @@ def lib():
     L.xcg_cache_size.restype = C.c_uint64
     L.xcg_cache_clear.argtypes = [vp]
     L.xcg_cache_clear.restype = C.c_int
+    L.xcg_cache_learn_batch.argtypes = [vp, u8p, C.c_uint64, u64p, vp]
+    L.xcg_cache_learn_batch.restype = C.c_int
+    L.xcg_cache_learn_host.argtypes = [vp, u8p, C.c_uint64, u64p]
+    L.xcg_cache_learn_host.restype = C.c_int
+    L.xcg_cache_export.argtypes = [vp, u8p, u64p, C.c_uint64, C.POINTER(C.c_uint64), vp]
+    L.xcg_cache_export.restype = C.c_int
+    L.xcg_cache_export_host.argtypes = [vp, u8p, u64p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.xcg_cache_export_host.restype = C.c_int
     L.xcg_last_rounds.argtypes = [vp]
     L.xcg_last_rounds.restype = C.c_int
     L.xcg_ctx_destroy.argtypes = [vp]
@@ -324,6 +332,58 @@ class Context:
         """enter (or replace the bytes of) one segment -- XCodecPipePair's <LEARN>."""
         assert len(seg) == 2048
         _check(lib().xcg_cache_enter_host(self.h, C.c_uint64(h), (C.c_uint8 * 2048).from_buffer_copy(seg)))
+
+    def cache_learn_device(self, d_segs, n: int, d_hash=None, stream=None):
+        """xcg_cache_learn_batch on device tensors: the n segments at
+        d_segs.data_ptr() (any alignment), their hashes into d_hash (int64
+        tensor, or None).  Ordered on `stream`; no synchronisation is needed
+        before the context's next batch."""
+        _check(lib().xcg_cache_learn_batch(
+            self.h, C.c_void_p(d_segs.data_ptr()), int(n),
+            C.c_void_p(d_hash.data_ptr()) if d_hash is not None else None, _stream_ptr(stream)))
+
+    def cache_learn(self, segs) -> np.ndarray:
+        """Learn whole 2048-byte segments (bytes / np.uint8, back to back) in
+        order, as n <LEARN>s (xcg_cache_learn_host).  Returns their XCodecHash
+        values (np.uint64)."""
+        a = np.frombuffer(segs, dtype=np.uint8) if not isinstance(segs, np.ndarray) else np.ascontiguousarray(segs)
+        if a.size % SEG:
+            raise ValueError('segments are 2048 bytes each')
+        n = a.size // SEG
+        hs = np.zeros(n, dtype=np.uint64)
+        if n:
+            _check(lib().xcg_cache_learn_host(self.h, a.ctypes.data, n, hs.ctypes.data))
+        return hs
+
+    def cache_export(self):
+        """Every live (hash, segment) of a memory cache, nothing changed: a
+        bounded cache least recently used first, an unbounded one by ascending
+        hash (xcg_cache_export_host).  Returns (hashes np.uint64, bytes)."""
+        cnt = C.c_uint64()
+        rc = lib().xcg_cache_export_host(self.h, None, None, 0, C.byref(cnt))
+        if rc != XCG_EOVERFLOW:
+            _check(rc)
+        n = int(cnt.value)
+        hs = np.zeros(n, dtype=np.uint64)
+        segs = np.zeros(n * SEG, dtype=np.uint8)
+        if n:
+            _check(lib().xcg_cache_export_host(self.h, segs.ctypes.data, hs.ctypes.data, n, C.byref(cnt)))
+        return hs, segs.tobytes()
+
+    def cache_save(self, path: str):
+        """Write the cache as `tack -p`'s persistent cache file: the segments
+        back to back, in export order (programs/tack/tack.cc:103-127)."""
+        _, segs = self.cache_export()
+        with open(path, 'wb') as f:
+            f.write(segs)
+
+    def cache_load(self, path: str) -> np.ndarray:
+        """Learn every segment of a `tack -p` file, in file order."""
+        with open(path, 'rb') as f:
+            data = f.read()
+        if len(data) % SEG:
+            raise ValueError('Corrupt persistent cache')
+        return self.cache_learn(data)
 
     def pair_stats(self):
         """(primary entries, this front's disk index entries, disk entries
