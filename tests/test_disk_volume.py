@@ -7,6 +7,8 @@ same reopen (which writes only the registry entries of fronts it collects).  A m
 damaged file reopens without a crash."""
 import importlib.util
 import os
+import re
+import subprocess
 
 import pytest
 
@@ -19,6 +21,19 @@ SEG = 2048
 
 def _uuid(k):
     return '%08x-0000-4000-8000-%012x' % (0xF11E, k)
+
+
+def _harness_reopen(src, disk, out):
+    """The same reopen and save by the volume unit on its own (oracle/
+    volume_harness.cc: wanproxy_amd/csrc/xcg_volume.cpp under AddressSanitizer
+    and UndefinedBehaviorSanitizer, a child process): the bytes it wrote."""
+    harness = os.path.join(os.path.dirname(HERE), 'oracle/build/volume_harness')
+    if not os.path.exists(harness):
+        from oracle import lib
+        lib.build()
+    r = subprocess.run([harness, 'reopen', str(src), str(disk), str(out)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stderr == '', r.stderr
+    return open(out, 'rb').read()
 
 
 @pytest.mark.parametrize('nb,parts,peer', [(3, 1, False), (3, 3, True), (12, 2, True)])
@@ -54,6 +69,8 @@ def test_reopen_and_save_is_the_reference_file(ref_oracle, tmp_path, nb, parts, 
     if a != b:
         i = next(j for j in range(len(a)) if a[j] != b[j])
         pytest.fail(f'reopened volume saved differently: first byte {i} (block {i // SEG})')
+    h = _harness_reopen(vref, disk, tmp_path / 'harness.vol')
+    assert h == a and h == b
 
 
 def test_fresh_and_damaged_volumes(tmp_path):
@@ -65,6 +82,7 @@ def test_fresh_and_damaged_volumes(tmp_path):
     K.close()
     fresh = open(tmp_path / 'fresh.vol', 'rb').read()
     assert len(fresh) == disk and fresh == bytes(disk)
+    assert _harness_reopen(tmp_path / 'absent.vol', disk, tmp_path / 'fresh.harness') == fresh
     # damaged files reopen (their index entries fail the reload's checks or
     # read as empty) and save without a crash
     import numpy as np
@@ -77,3 +95,10 @@ def test_fresh_and_damaged_volumes(tmp_path):
         K.save(str(tmp_path / (name + '.out')))
         K.close()
         assert os.path.getsize(tmp_path / (name + '.out')) == disk
+        # the volume unit on its own writes the same bytes -- but for xuid 0's
+        # registry slot: noise holds no UUID, so each reopen generates a local
+        # one there (registry_load, xcodec_cache_disk.cc:575-596), at random
+        h, lib_out = _harness_reopen(p, disk, tmp_path / (name + '.harness')), (tmp_path / (name + '.out')).read_bytes()
+        assert len(h) == disk and h[36:] == lib_out[36:]
+        for u in (h[:36], lib_out[:36]):
+            assert re.fullmatch(rb'[0-9a-f]{8}-[0-9a-f]{4}-4[0-9a-f]{3}-[89ab][0-9a-f]{3}-[0-9a-f]{12}', u)

@@ -183,7 +183,8 @@ struct LruBatch {
   uint32_t* enter_base;   // [n + 1]
 };
 
-// XCodecCachePair of a bounded memory primary and a disk secondary (xcg_pair.hip).
+// XCodecCachePair of a bounded memory primary and a disk secondary (the state
+// objects' life cycle: xcg_pair_state.hip; the replay engine: xcg_pair.hip).
 // The disk (XcgDiskState) is shared by every pair front on it, as XCodecDisk is
 // by its XCodecDiskCache front-ends.
 struct XcgDiskState;
@@ -215,7 +216,6 @@ extern "C" void xcg_pair_state_destroy(XcgPairState* P);
 extern "C" int xcg_pair_state_clear(XcgPairState* P);
 extern "C" void xcg_pair_state_stats(const XcgPairState* P, uint64_t* st);
 extern "C" uint32_t xcg_pair_state_last_base(const XcgPairState* P);
-extern "C" uint32_t xcg_pair_state_limit(const XcgPairState* P);
 extern "C" uint32_t xcg_pair_state_disk_blocks(const XcgPairState* P);
 extern "C" XcgDiskState* xcg_pair_state_disk(const XcgPairState* P);
 extern "C" const uint64_t* xcg_pair_state_ptime(const XcgPairState* P);

@@ -15,6 +15,7 @@
 #pragma once
 #include "xcg_args.h"
 #include "xcg_device.h"
+#include "xcg_segment.h"   // host_seg_hash
 
 namespace xcg {
 
@@ -65,17 +66,6 @@ struct FiltSet {
   uint32_t gmask;
 };
 
-// XCodecHash::hash of one whole segment (xcodec/xcodec_hash.h:166-174) on the host.
-inline uint64_t host_seg_hash(const uint8_t* w) {
-  uint32_t s1 = 0, s2 = 0, b1 = 0, b2 = 0;
-  for (uint32_t k = 0; k < 2048; ++k) {
-    s1 += (uint32_t)w[k] + 1u;
-    s2 += s1;
-    b1 += w[k] ? (uint32_t)__builtin_ctz(w[k]) + 1u : 0u;
-    b2 += b1;
-  }
-  return ((uint64_t)((b1 << 16) + b2) << 36) + (uint64_t)((s1 << 20) + s2);
-}
 inline unsigned grid_for(uint64_t threads) { return (unsigned)((threads + 255) / 256); }   // 256-thread blocks
 // The persistent cache's table and filters (host side: what the drivers hand the kernels).
 inline HashTab tab_of(const XcgCacheView& g) { return HashTab{g.keys, g.vals, g.mask}; }

@@ -4,9 +4,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "xcg_segment.h"   // SEG
+
 namespace xcg {
 
-constexpr int SEG = 2048;                // XCODEC_SEGMENT_LENGTH, xcodec/xcodec.h:87
 constexpr uint32_t MAGIC = 0xF1u;        // XCODEC_MAGIC, xcodec/xcodec.h:30
 constexpr uint32_t OP_ESCAPE = 0x00u;    // xcodec/xcodec.h:42
 constexpr uint32_t OP_EXTRACT = 0x01u;   // xcodec/xcodec.h:60

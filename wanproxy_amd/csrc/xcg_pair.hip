@@ -62,6 +62,13 @@
 // the batch's declarations to its end): a sub-batch writes less than a disk lap,
 // which guarantees that.  The commit then places the final primary residents,
 // writes the appended disk blocks and rebuilds G -- all on the device.
+//
+// This unit is the engine: the replay, the commit and the encode / decode
+// entry points.  The two state objects it works on (XcgDiskState,
+// XcgPairState: xcg_pair_state.h) are created, bound to a device, mapped (the
+// pool), saved, reopened, counted and destroyed by xcg_pair_state.hip; the
+// volume file (registry, index blocks and their counters, the reload, the
+// clock of a reloaded ring) belongs to xcg_volume.{h,cpp}, host code only.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_radix_sort_config.hpp>
@@ -71,122 +78,21 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <ctype.h>
-#include <errno.h>
-#include <fcntl.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
 #include <algorithm>
 #include <chrono>
-#include <map>
-#include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "xcg_cache.h"
 #include "xcg_args.h"
+#include "xcg_pair_state.h"
 
 namespace xcg {
 
-constexpr uint32_t DISK_ENTRIES = 204;   // XCDFS_ENTRIES_PER_INDEX_BLOCK, xcodec_cache_disk.cc:87
-constexpr uint64_t NOENT = ~0ull;        // no disk entry
-constexpr uint64_t NOKEY = ~0ull;
 constexpr uint64_t NEVERT = ~0ull;       // ptime: visible to the end
-constexpr uint32_t NIL = 0xFFFFFFFFu;
 
 // Position kinds.  A position is a pseudo reference (the primary at the start,
 // LRU order) or a recorded row.
 enum : uint8_t { K_PSEUDO = 0, K_ENTER = 1, K_LOOKUP = 2, K_GMISS = 3, K_SKIP = 4, K_REPL = 5 };
-
-struct PairCnt {                          // device counters of one pass
-  uint32_t split;                         // a row list overflowed: a smaller sub-batch
-  uint32_t nbad;                          // recorded lookups the replay contradicts
-  uint32_t unsorted;                      // a chunk's rows out of time order
-  uint32_t changed;                       // touches moved (fixed-point round) / ptime moved (decode)
-  uint32_t nslow;                         // stack-distance queries for the block table
-  uint32_t nmove, nstage, nomiss;         // commit moves, staged moves
-  uint32_t nohit;                         // (decode) a HIT with no earlier definer
-  uint32_t pad[7];
-};
-
-struct PairDev {
-  // the front
-  uint32_t C, xuid, P;                    // limit, front id, primary entries at the start
-  uint64_t* pkey;                         // [C]
-  uint64_t* pdisk;                        // [C] number of the same hash's disk entry (NOENT)
-  const uint32_t* lru;                    // [P] slots, least recent first
-  uint64_t* ptime;                        // [C + D]
-  // the disk
-  uint32_t D, nb;
-  uint64_t dclock0;
-  uint64_t* dkey;                         // [D]
-  uint64_t* dent;                         // [D]
-  uint32_t* dxuid;                        // [D]
-  // rows
-  int dec;                                // decode rows (packed, REPLACE flags) vs encode rows
-  uint32_t n, maxd, maxe;
-  const uint4* ev;
-  const uint32_t* nev;                    // encode: rows per chunk
-  const uint64_t* base64;                 // decode: row base per chunk
-  const uint64_t* cnt64;                  // decode: rows per chunk
-  uint32_t* pbase;                        // encode: position base per chunk (exclusive scan) [n + 1]
-  uint32_t* pcnt;                         // encode: rows per chunk [n + 1]
-  // positions [np)
-  uint32_t newb, etot, np;
-  uint32_t* ent;                          // entity (decode REPL rows: the replaced entity)
-  uint32_t* yent;                         // decode REPL rows: the new entity (else NIL)
-  uint8_t* kind;
-  uint64_t* tim;                          // stream time (chunk << 21 | t)
-  uint64_t* hsh;
-  uint32_t* skey;                         // sort input keys (entity, etot = none) / values (position)
-  uint32_t* sval;
-  uint32_t* sk;                           // sorted
-  uint32_t* sv;
-  int32_t* prv;                           // previous reference of the same entity (-1)
-  int32_t* nxt;                           // next reference (-1)
-  uint32_t* isr;                          // 1: a reference [np + 1]
-  uint32_t* rc;                           // exclusive prefix of isr [np + 1]
-  uint8_t* phit;                          // primary hit (a lookup / GMISS whose entity is resident)
-  uint32_t* app;                          // appends at the position [np + 1]
-  uint32_t* clk;                          // exclusive prefix of app [np + 1]
-  uint32_t* elast;                        // [etot] position of the entity's last append (NIL)
-  uint8_t* tflag;                         // [np] a touch at the position
-  uint64_t* ddeath;                       // [np] death clock of the entity's disk entry current at the row
-  uint32_t* erep;                         // [newb] (decode) position of the REPLACE that ends it (NIL)
-  uint32_t* erun;                         // [etot] sorted index of the entity's first element (NIL)
-  uint32_t* erend;                        // [etot] one past its last element
-  uint64_t* einit;                        // [etot] disk entry current before the entity's first element
-  uint32_t* ecov;                         // [etot] (leave) initial coverage end (NIL: to the end)
-  uint32_t* egap;                         // [etot] (leave) first uncovered position found at a span start
-  uint32_t* etail;                        // [etot] (leave) coverage end after the entity's last element
-  uint64_t* sa;                           // [np + 1] segmented-scan input / output
-  uint64_t* sb;
-  uint32_t* nq;                           // [np + 1] next element of the run that can touch (NIL)
-  uint8_t* tnew;                          // [np + 1] touches of the running round
-  uint32_t* slow;                         // positions for the block table
-  uint32_t* tab;                          // [nbk * (nbk + 1)] 2-D prefix counts
-  uint32_t bsh, nbk;                      // table block = 1 << bsh positions
-  uint32_t* f1;                           // misses / final residents [np + 1]
-  uint32_t* f2;                           // terminals / new residents [np + 1]
-  uint32_t* r1;                           // exclusive prefixes [np + 1]
-  uint32_t* r2;
-  uint32_t* missrow;                      // position of the i-th miss
-  uint32_t* occ;                          // [C] slot kept / free list
-  uint32_t* freel;                        // [C]
-  uint32_t* lru2;                         // [C] the next LRU order
-  uint4* moves;                           // commit moves
-  PairCnt* cnt;
-  HashTab bm;                             // hash -> ENTER position (encode)
-  HashTab g;                              // the front's G (leave: which disk blocks are entities)
-  uint32_t* need;                         // per chunk: flagged; earliest / latest contradicted time
-  uint32_t* bad_t;
-  uint32_t* bad_hi;
-};
-
-__device__ __forceinline__ uint64_t death_of(uint64_t e, uint32_t nb) {
-  return e == NOENT ? 0ull : (uint64_t)DISK_ENTRIES * (e / DISK_ENTRIES + nb);
-}
 
 // The live disk entry an initial entity (id < newb) had at the pass start.
 __device__ __forceinline__ uint64_t e0_of(const PairDev& d, uint32_t x) {
@@ -1099,147 +1005,10 @@ __global__ __launch_bounds__(256) void pair_seed_events_kernel(uint32_t n, const
   if (lane_id() == 0) nev[c] = row;
 }
 
-// Statistics: this front's live disk entries (xuid) or every live entry (xuid ~0).
-__global__ __launch_bounds__(256) void pair_count_live_kernel(const uint64_t* dent, const uint32_t* dxuid, uint32_t D,
-                                                              uint32_t nb, uint64_t dclock, uint32_t xuid,
-                                                              uint32_t* out) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  bool live = false;
-  if (i < D) {
-    const uint64_t e = dent[i];
-    live = e != NOENT && dclock < death_of(e, nb) && (xuid == NIL || dxuid[i] == xuid);
-  }
-  const uint64_t m = ballot(live);
-  if (lane_id() == 0 && m) atomicAdd(out, (uint32_t)__builtin_popcountll(m));
-}
-
-// A front goes away or is cleared: its disk entries leave the index (the
-// volume's index blocks keep them unless the whole volume is reset).
-__global__ __launch_bounds__(256) void pair_drop_front_kernel(uint64_t* dkey, uint64_t* dent, const uint32_t* dxuid,
-                                                              uint32_t D, uint32_t xuid) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < D && (xuid == NIL || dxuid[i] == xuid)) {
-    dent[i] = NOENT;
-    if (xuid == NIL) dkey[i] = NOKEY;
-  }
-}
-
 }  // namespace xcg
 
 // ---------------------------------------------------------------------------
-// Host side: the state objects and the passes' drivers.
-
-struct XcgPairState;
-
-// One XCodecDisk: the ring's blocks (device arrays) and the fronts on it.
-struct XcgDiskState {
-  xcg::DevMem mem;                 // the ring's device arrays
-  uint64_t nb = 0;                 // index blocks
-  uint32_t D = 0;                  // nb * 204 data blocks
-  uint64_t dclock = 0;             // entries written to the disk (every front)
-  int device = -1;                 // bound by the first front
-  uint64_t* dkey = nullptr;
-  uint64_t* dent = nullptr;
-  uint32_t* dxuid = nullptr;
-  // the data blocks' bytes: one physical allocation mapped behind every front's primary
-  uint32_t flags = 0;              // XCG_DISK_* (xcgpu.h)
-  int tier = -1;                   // where the blocks live: 0 HBM, 1 pinned host memory (-1: not yet)
-  bool vmm = false;
-  hipMemGenericAllocationHandle_t pool_h{};
-  size_t pool_bytes = 0;
-  void* dva = nullptr;             // the disk's own mapping of pool_h, for its whole life (xcg_disk_save)
-  std::vector<XcgPairState*> fronts;   // by xuid (nullptr: free)
-  // the volume (xcodec_cache_disk.cc:72-101): its size, per index block the
-  // counter it was last written with, the counter of the block being filled,
-  // the registry's blocks and the UUID each xuid has there
-  uint64_t bytes = 0;
-  std::vector<uint64_t> ctr;
-  uint64_t ibc = 1;
-  std::vector<uint8_t> reg;
-  std::vector<std::string> uuid;
-  // a reopened volume's ring, waiting for the first front's device
-  bool pending = false;
-  bool ring_loaded = false;
-  bool zeroed = false;             // a fresh volume's blocks read as zeros (as the reference's ftruncate'd file)
-  std::vector<uint64_t> h_key, h_ent;
-  std::vector<uint32_t> h_xuid;
-  std::vector<uint8_t> h_data;
-  // without HIP virtual memory every front has its own copy of the blocks: a
-  // front that goes away leaves the blocks it wrote here (shadow_ok: per block)
-  std::vector<uint8_t> shadow, shadow_ok;
-  int refs = 1;                    // the creator's reference + one per front
-};
-
-struct XcgPairState {
-  xcg::DevMem mem;                 // the front's arrays, the pass scratch, a pool without virtual memory
-  uint32_t C = 0;                  // primary limit in segments
-  // XCodecCachePair over an unbounded XCodecMemoryCache (limit 0: enter never
-  // evicts, xcodec_cache.h:303-318): C is then only the primary's capacity,
-  // and a commit that would evict fails (XCG_EOVERFLOW) instead
-  bool unbounded = false;
-  uint32_t D = 0, nb = 0;
-  XcgDiskState* disk = nullptr;
-  uint16_t xuid = 0;
-  uint32_t pcount = 0;             // primary entries
-  uint64_t gclock = 0;             // disk clock when G was last rebuilt
-  bool gstale = false;
-  // device state
-  uint64_t* pkey = nullptr;        // [C]
-  uint64_t* pdisk = nullptr;       // [C]
-  uint32_t* lru = nullptr;         // [C]
-  uint32_t* lru2 = nullptr;        // [C]
-  uint64_t* ptime = nullptr;       // [C + D]
-  // the pool (C primary segments, then the disk's blocks)
-  uint8_t* pool = nullptr;
-  bool pool_vmm = false;
-  void* va = nullptr;
-  size_t va_bytes = 0, prim_bytes = 0;
-  hipMemGenericAllocationHandle_t prim_h{};
-  // pass scratch, grown on demand
-  uint64_t np_cap = 0, n_cap = 0, et_cap = 0, tab_cap = 0, stg_cap = 0, tmp_cap = 0, bm_cap = 0, hk_cap = 0;
-  uint32_t* ent = nullptr; uint32_t* yent = nullptr; uint8_t* kind = nullptr; uint64_t* tim = nullptr;
-  uint64_t* hsh = nullptr; uint32_t* skey = nullptr; uint32_t* sval = nullptr; uint32_t* sk = nullptr;
-  uint32_t* sv = nullptr; int32_t* prv = nullptr; int32_t* nxt = nullptr; uint32_t* isr = nullptr;
-  uint32_t* rc = nullptr; uint8_t* phit = nullptr; uint32_t* app = nullptr; uint32_t* clk = nullptr;
-  uint32_t* slow = nullptr; uint32_t* f1 = nullptr; uint32_t* f2 = nullptr; uint32_t* r1 = nullptr;
-  uint32_t* r2 = nullptr; uint32_t* missrow = nullptr; uint4* moves = nullptr;
-  uint32_t* pbase = nullptr;       // [n + 1]
-  uint32_t* pcnt = nullptr;        // [n + 1]
-  uint32_t* elast = nullptr;       // [etot]
-  uint64_t el_cap = 0;
-  uint8_t* tflag = nullptr;        // [np]
-  uint64_t* ddeath = nullptr;      // [np]
-  uint32_t* erep = nullptr;        // [C + D]
-  uint32_t* erun = nullptr;        // [etot]
-  uint32_t* erend = nullptr;       // [etot]
-  uint64_t* einit = nullptr;       // [etot]
-  uint32_t* ecov = nullptr; uint32_t* egap = nullptr; uint32_t* etail = nullptr;   // [etot]
-  uint64_t* sa = nullptr; uint64_t* sb = nullptr;   // [np + 1] segmented scans
-  uint32_t* nq = nullptr;          // [np + 1]
-  uint8_t* tnew = nullptr;         // [np + 1]
-  uint64_t ex_cap = 0;
-  uint32_t* tab = nullptr;         // block table + its segment sums
-  uint32_t* occ = nullptr; uint32_t* freel = nullptr; uint32_t* ofl = nullptr; uint32_t* ofr = nullptr;
-  uint64_t* hk = nullptr; uint64_t* hk2 = nullptr; uint32_t* hv = nullptr; uint32_t* hv2 = nullptr;
-  uint64_t* bm_keys = nullptr; uint64_t* bm_vals = nullptr;
-  uint8_t* staging = nullptr;
-  void* tmp = nullptr;
-  xcg::PairCnt* cnt = nullptr;
-  uint32_t* h_small = nullptr;     // pinned: small readbacks
-  xcg::PairCnt* h_cnt = nullptr;   // pinned
-  // the last pass (kept for the commit)
-  xcg::PairDev last{};
-  uint32_t last_M = 0;
-  bool last_ranked = false;
-  uint64_t last_appends = 0;
-  // sub-batch bookkeeping
-  uint64_t appends = 0;            // disk blocks the last committed sub-batch wrote
-  uint32_t last_base = 0;
-  int prev_passes = 1;
-  // chunks per sub-batch the last committed sub-batch's disk writes imply (90 %
-  // of a lap at its rate; 0: none yet); the next call starts from it
-  uint32_t fit_per = 0;
-};
+// Host side: the passes' drivers (the state objects: xcg_pair_state.h).
 
 namespace {
 
@@ -1252,11 +1021,6 @@ using namespace xcg;
 // stable, which the entity runs need (positions stay in order).
 using PairSortCfg = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
                                                rocprim::default_config, 0>;
-
-bool pair_debug() {
-  static const bool on = getenv("XCG_PAIR_DEBUG") != nullptr;
-  return on;
-}
 
 // Guesses of a sub-batch's tiling seed replayed before its first parse
 // (read per sub-batch).  Default 1: on C5-PAIR-LAPS three guesses save two of
@@ -1394,7 +1158,7 @@ int replay(XcgPairState* P, const RowSrc& rs, const HashTab& g, bool want_leave,
   PairDev d{};
   d.C = P->C; d.xuid = P->xuid; d.P = P->pcount;
   d.pkey = P->pkey; d.pdisk = P->pdisk; d.lru = P->lru; d.ptime = P->ptime;
-  d.D = P->D; d.nb = P->nb; d.dclock0 = K->dclock;
+  d.D = P->D; d.nb = P->nb; d.dclock0 = K->vol.dclock;
   d.dkey = K->dkey; d.dent = K->dent; d.dxuid = K->dxuid;
   d.dec = rs.dec; d.n = n; d.maxd = rs.maxd; d.maxe = rs.maxe; d.ev = rs.ev; d.nev = rs.nev;
   d.base64 = rs.base64; d.cnt64 = rs.cnt64;
@@ -1552,15 +1316,6 @@ int replay(XcgPairState* P, const RowSrc& rs, const HashTab& g, bool want_leave,
   return 0;
 }
 
-// The primary's arrays must outlive one replay; the commit's slot arrays too.
-int ensure_front_arrays(XcgPairState* P) {
-  if (P->occ) return 0;
-  DevMem& m = P->mem;
-  return m.dev(&P->occ, 4ull * P->C) && m.dev(&P->freel, 4ull * P->C) && m.dev(&P->ofl, 4ull * (P->C + 1)) &&
-                 m.dev(&P->ofr, 4ull * (P->C + 1))
-             ? 0 : -5;
-}
-
 // G from the state: wipe, then every primary slot and live own disk block.
 void pair_rebuild(XcgPairState* P, const PairGpu& G, hipStream_t st) {
   const HashTab g = tab_of(G.g);
@@ -1570,8 +1325,9 @@ void pair_rebuild(XcgPairState* P, const PairGpu& G, hipStream_t st) {
   XcgDiskState* K = P->disk;
   hipLaunchKernelGGL(pair_rebuild_kernel, dim3(grid_for((uint64_t)P->C + P->D)), dim3(256), 0, st,
                      (const uint64_t*)P->pkey, P->C, (const uint64_t*)K->dkey, (const uint64_t*)K->dent,
-                     (const uint32_t*)K->dxuid, P->D, P->nb, (uint32_t)P->xuid, K->dclock, g, fs, G.g.nseg, G.status);
-  P->gclock = K->dclock;
+                     (const uint32_t*)K->dxuid, P->D, P->nb, (uint32_t)P->xuid, K->vol.dclock, g, fs, G.g.nseg,
+                     G.status);
+  P->gclock = K->vol.dclock;
   P->gstale = false;
 }
 
@@ -1598,7 +1354,7 @@ int pair_commit(XcgPairState* P, const PairGpu& G, hipStream_t st) {
   }
   // the primary never evicts: its capacity is exceeded
   if (P->unbounded && (int64_t)d.P + (int64_t)P->last_M - (int64_t)P->C > 0) return -75;
-  const uint64_t dend = K->dclock + P->last_appends;
+  const uint64_t dend = K->vol.dclock + P->last_appends;
   if (hipMemsetAsync(P->occ, 0, 4ull * P->C, st) != hipSuccess ||
       hipMemsetAsync(&P->cnt->nmove, 0, 8, st) != hipSuccess)
     return -5;
@@ -1627,13 +1383,7 @@ int pair_commit(XcgPairState* P, const PairGpu& G, hipStream_t st) {
   }
   std::swap(P->lru, P->lru2);
   P->pcount = pc;
-  // index blocks filled by this commit are written with the running counter
-  // (XCodecDisk::enter, xcodec_cache_disk.cc:708-738; 0 means unused)
-  for (uint64_t m = K->dclock / DISK_ENTRIES + 1; m <= dend / DISK_ENTRIES; ++m) {
-    K->ctr[(m - 1) % K->nb] = K->ibc;
-    if (++K->ibc == 0) K->ibc = 1;
-  }
-  K->dclock = dend;
+  volume_advance(&K->vol, P->last_appends);          // (the clock is now dend)
   P->appends = P->last_appends;
   pair_rebuild(P, G, st);
   return hipStreamSynchronize(st) == hipSuccess && hipGetLastError() == hipSuccess ? 0 : -5;
@@ -1648,7 +1398,7 @@ int fill_ptime(XcgPairState* P, hipStream_t st) {
 // since G was built): rebuild G before this front looks anything up.
 int pair_sync_front(XcgPairState* P, const PairGpu& G, hipStream_t st) {
   XcgDiskState* K = P->disk;
-  if (!P->gstale && K->dclock / DISK_ENTRIES == P->gclock / DISK_ENTRIES) return 0;
+  if (!P->gstale && K->vol.dclock / DISK_ENTRIES == P->gclock / DISK_ENTRIES) return 0;
   pair_rebuild(P, G, st);
   return hipStreamSynchronize(st) == hipSuccess && hipGetLastError() == hipSuccess ? 0 : -5;
 }
@@ -1662,711 +1412,9 @@ PairGpu gpu_of(const XcgStreamArgs& a) {
   return G;
 }
 
-// The disk's device arrays, on the first front's device.
-int disk_bind(XcgDiskState* K, int device) {
-  if (K->device >= 0) return K->device == device ? 0 : -22;
-  const uint64_t D = K->D;
-  if (!(K->mem.dev(&K->dkey, 8 * D) && K->mem.dev(&K->dent, 8 * D) && K->mem.dev(&K->dxuid, 4 * D)) ||
-      hipMemset(K->dkey, 0xFF, 8 * D) != hipSuccess ||
-      hipMemset(K->dent, 0xFF, 8 * D) != hipSuccess || hipMemset(K->dxuid, 0xFF, 4 * D) != hipSuccess) {
-    K->mem.release_all();
-    K->dkey = K->dent = nullptr;
-    K->dxuid = nullptr;
-    return -12;
-  }
-  K->device = device;
-  return 0;
-}
-
-// The front's pool: C primary segments followed by the disk's D blocks at
-// pool + (C + i) * 2048.  HIP virtual memory maps the disk's one physical
-// allocation behind every front; without it each front allocates its own copy
-// (a front reads only the blocks it wrote itself, so that is correct too).
-int map_pool(XcgPairState* P, int device) {
-  XcgDiskState* K = P->disk;
-  if (!getenv("XCG_NO_VMM")) {
-    hipMemAllocationProp prop{};
-    prop.type = hipMemAllocationTypePinned;
-    prop.location.type = hipMemLocationTypeDevice;
-    prop.location.id = device;
-    size_t gran = 0;
-    bool ok = hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityMinimum) == hipSuccess &&
-              gran > 0;
-    if (ok && !K->vmm && K->pool_bytes == 0) {
-      // The disk's blocks: HBM, unless the volume does not fit beside what the
-      // device already holds (keep 4 GiB free) or the caller asks for the host
-      // tier -- then pinned host memory behind the same addresses, which the
-      // kernels read and write over PCIe (a spill level below HBM).
-      const size_t sd = align_up((size_t)K->D * SEG + 256, gran);
-      size_t fr = 0, tot = 0;
-      const bool fits = hipMemGetInfo(&fr, &tot) == hipSuccess && fr > sd + (4ull << 30);
-      const bool want_host = (K->flags & 1u) != 0 || (!(K->flags & 2u) && !fits);
-      if (!want_host && hipMemCreate(&K->pool_h, sd, &prop, 0) == hipSuccess) {
-        K->pool_bytes = sd;
-        K->vmm = true;
-        K->tier = 0;
-      } else if (!(K->flags & 2u)) {
-        (void)hipGetLastError();
-        hipMemAllocationProp hp{};
-        hp.type = hipMemAllocationTypePinned;
-        hp.location.type = hipMemLocationTypeHost;
-        hp.location.id = 0;
-        size_t hg = 0;
-        const hipError_t e1 = hipMemGetAllocationGranularity(&hg, &hp, hipMemAllocationGranularityMinimum);
-        const hipError_t e2 = e1 == hipSuccess && hg && gran % hg == 0 ? hipMemCreate(&K->pool_h, sd, &hp, 0)
-                                                                        : hipErrorInvalidValue;
-        if (e2 == hipSuccess) {
-          K->pool_bytes = sd;
-          K->vmm = true;
-          K->tier = 1;
-        } else {
-          // (host-located VMM needs a runtime that has it: ROCm 7.2's does, the
-          // 7.0 runtime PyTorch bundles refuses it) -- stay on the device
-          if (pair_debug())
-            fprintf(stderr, "pair: host tier not available (granularity %s %zu, create %s)\n", hipGetErrorString(e1),
-                    hg, hipGetErrorString(e2));
-          (void)hipGetLastError();
-          if (hipMemCreate(&K->pool_h, sd, &prop, 0) == hipSuccess) {
-            K->pool_bytes = sd;
-            K->vmm = true;
-            K->tier = 0;
-          }
-        }
-      }
-    }
-    ok = ok && K->vmm;
-    if (ok && !K->dva) {
-      // The disk's own mapping of its blocks, held until the disk goes: the
-      // volume can be saved after every front is gone, and the allocation
-      // always has a mapping until it is released (fronts come and go).
-      void* va = nullptr;
-      hipMemAccessDesc acc{};
-      acc.location = prop.location;
-      acc.flags = hipMemAccessFlagsProtReadWrite;
-      bool m = false;
-      bool dok = hipMemAddressReserve(&va, K->pool_bytes, 0, nullptr, 0) == hipSuccess;
-      dok = dok && (m = hipMemMap(va, K->pool_bytes, 0, K->pool_h, 0) == hipSuccess);
-      dok = dok && hipMemSetAccess(va, K->pool_bytes, &acc, 1) == hipSuccess;
-      if (dok) {
-        K->dva = va;
-      } else {
-        if (m) (void)hipMemUnmap(va, K->pool_bytes);
-        if (va) (void)hipMemAddressFree(va, K->pool_bytes);
-        (void)hipGetLastError();
-      }
-    }
-    const size_t sp = align_up((size_t)P->C * SEG, gran ? gran : 1);
-    bool prim = false, reserved = false, m1 = false, m2 = false;
-    if (ok) prim = ok = hipMemCreate(&P->prim_h, sp, &prop, 0) == hipSuccess;
-    if (ok) reserved = ok = hipMemAddressReserve(&P->va, sp + K->pool_bytes, 0, nullptr, 0) == hipSuccess;
-    if (ok) m1 = ok = hipMemMap(P->va, sp, 0, P->prim_h, 0) == hipSuccess;
-    if (ok) m2 = ok = hipMemMap((char*)P->va + sp, K->pool_bytes, 0, K->pool_h, 0) == hipSuccess;
-    if (ok) {
-      hipMemAccessDesc acc{};
-      acc.location = prop.location;
-      acc.flags = hipMemAccessFlagsProtReadWrite;
-      ok = hipMemSetAccess(P->va, sp + K->pool_bytes, &acc, 1) == hipSuccess;
-    }
-    if (!ok && pair_debug())
-      fprintf(stderr, "pair: pool mapping failed (prim %d reserved %d map %d/%d tier %d): %s\n", (int)prim, (int)reserved,
-              (int)m1, (int)m2, K->tier, hipGetErrorString(hipGetLastError()));
-    if (ok) {
-      P->pool_vmm = true;
-      P->prim_bytes = sp;
-      P->va_bytes = sp + K->pool_bytes;
-      P->pool = (uint8_t*)P->va + sp - (size_t)P->C * SEG;
-      return 0;
-    }
-    if (m2) (void)hipMemUnmap((char*)P->va + sp, K->pool_bytes);
-    if (m1) (void)hipMemUnmap(P->va, sp);
-    if (reserved) (void)hipMemAddressFree(P->va, sp + K->pool_bytes);
-    if (prim) (void)hipMemRelease(P->prim_h);
-    P->va = nullptr;
-    (void)hipGetLastError();
-  }
-  if (!P->mem.dev(&P->pool, ((uint64_t)P->C + P->D) * SEG + 256)) return -12;
-  P->pool_vmm = false;
-  return 0;
-}
-
-void unmap_pool(XcgPairState* P) {
-  if (P->pool_vmm) {
-    (void)hipDeviceSynchronize();
-    (void)hipMemUnmap((char*)P->va + P->prim_bytes, P->va_bytes - P->prim_bytes);
-    (void)hipMemUnmap(P->va, P->prim_bytes);
-    (void)hipMemAddressFree(P->va, P->va_bytes);
-    (void)hipMemRelease(P->prim_h);
-  } else {
-    P->mem.release(P->pool);
-  }
-  P->pool = nullptr;
-}
-
-constexpr uint32_t REG_BLOCKS = 18, REG_ENTRIES = 2048 / 36, CHECK_BOUNDARY = 80, XUIDS = 1024;
-
-// XCodecDisk::registry_write (xcodec_cache_disk.cc:603-627): the xuid's
-// registry block with the UUID patched in, written back to block 0 (as the
-// reference does).
-void registry_write(XcgDiskState* K, uint32_t xuid, const char* u36) {
-  uint8_t blk[2048];
-  memcpy(blk, &K->reg[(xuid / REG_ENTRIES) * 2048], 2048);
-  memcpy(&blk[(xuid % REG_ENTRIES) * 36], u36, 36);
-  memcpy(&K->reg[0], blk, 2048);
-}
-
-// uuid_parse's format (common/uuid/uuid_libuuid.cc UUID::decode): 8-4-4-4-12 hex.
-bool uuid_ok(const uint8_t* u) {
-  for (int i = 0; i < 36; ++i) {
-    if (i == 8 || i == 13 || i == 18 || i == 23) {
-      if (u[i] != '-') return false;
-    } else if (!isxdigit(u[i])) {
-      return false;
-    }
-  }
-  return true;
-}
-
-// A reopened volume (XCodecDisk::XCodecDisk, xcodec_cache_disk.cc:107-237):
-// the registry gives the fronts; index blocks are scanned in block order up
-// to the first free one (counter 0); the lowest counter is the write head and
-// is not loaded; the rest load in counter order, a later entry of a hash
-// replacing an earlier one, the first and last 80 checked against their data
-// blocks (index_load_entries :408-478); fronts left without entries leave the
-// registry (registry_collect :496-528).  In the engine's clock model the write
-// head's entry 0 is clock 204 * (nb + head), and a block b loaded from the last
-// lap holds entries numbered from 204 * (nb + head - ((head - b) mod nb)): each
-// dies when the head reaches b again, as the reference invalidates it.
-//
-// Whole-range file I/O: one read()/write() moves at most 0x7ffff000 bytes on
-// Linux, so a volume past 2 GiB takes several.  A read that meets the end of
-// the file leaves the rest zero (the reference's ftruncate'd volume reads as
-// zeros there, xcodec_cache_disk.cc:853-860).
-bool pread_all(int fd, uint8_t* p, size_t n, off_t off) {
-  while (n > 0) {
-    const ssize_t r = pread(fd, p, n, off);
-    if (r < 0 && errno == EINTR) continue;
-    if (r < 0) return false;
-    if (r == 0) {
-      memset(p, 0, n);
-      return true;
-    }
-    p += r;
-    n -= (size_t)r;
-    off += r;
-  }
-  return true;
-}
-
-bool pwrite_all(int fd, const uint8_t* p, size_t n, off_t off) {
-  while (n > 0) {
-    const ssize_t r = pwrite(fd, p, n, off);
-    if (r < 0 && errno == EINTR) continue;
-    if (r <= 0) return false;
-    p += r;
-    n -= (size_t)r;
-    off += r;
-  }
-  return true;
-}
-
-// UUID::generate (common/uuid/uuid_libuuid.cc: uuid_generate + uuid_unparse):
-// a random (version 4) UUID in its 36-character lower-case form.
-bool gen_uuid(char out[37]) {
-  uint8_t b[16];
-  const int fd = ::open("/dev/urandom", O_RDONLY);
-  const bool ok = fd != -1 && pread_all(fd, b, 16, 0);
-  if (fd != -1) close(fd);
-  if (!ok) return false;
-  b[6] = (uint8_t)((b[6] & 0x0F) | 0x40);
-  b[8] = (uint8_t)((b[8] & 0x3F) | 0x80);
-  snprintf(out, 37, "%02x%02x%02x%02x-%02x%02x-%02x%02x-%02x%02x-%02x%02x%02x%02x%02x%02x", b[0], b[1], b[2], b[3],
-           b[4], b[5], b[6], b[7], b[8], b[9], b[10], b[11], b[12], b[13], b[14], b[15]);
-  return true;
-}
-
-int load_volume(XcgDiskState* K, int fd) {
-  const uint64_t nb = K->nb, D = K->D;
-  // the registry and index blocks; the data blocks go straight to h_data
-  std::vector<uint8_t> vol((REG_BLOCKS + nb) * 2048);
-  K->h_data.assign((size_t)D * SEG, 0);
-  if (!pread_all(fd, vol.data(), vol.size(), 0) ||
-      !pread_all(fd, K->h_data.data(), K->h_data.size(), (off_t)vol.size())) {
-    std::vector<uint8_t>().swap(K->h_data);
-    return -2;
-  }
-  memcpy(&K->reg[0], &vol[0], K->reg.size());
-  std::unordered_map<std::string, uint32_t> seen;
-  for (uint32_t x = 0; x < REG_BLOCKS * REG_ENTRIES && x < XUIDS; ++x) {
-    const uint8_t* u = &K->reg[(x / REG_ENTRIES) * 2048 + (x % REG_ENTRIES) * 36];
-    bool zero = true;
-    for (int i = 0; i < 36; ++i) zero &= u[i] == 0;
-    if (zero || !uuid_ok(u)) continue;
-    const std::string us((const char*)u, 36);
-    if (seen.count(us)) continue;
-    seen[us] = x;
-    K->uuid[x] = us;
-  }
-  if (seen.empty()) {                                       // registry_load: a local UUID (:575-596)
-    char u[37];
-    if (!gen_uuid(u)) return -2;
-    K->uuid[0] = std::string(u, 36);
-    registry_write(K, 0, u);
-  }
-  std::map<uint64_t, uint64_t> cmap;
-  uint64_t ibc = 0;
-  for (uint64_t o = 0; o < nb; ++o) {
-    uint64_t counter;
-    memcpy(&counter, &vol[(REG_BLOCKS + o) * 2048], 8);
-    if (counter == 0) {
-      cmap[0] = o;
-      break;
-    }
-    if (counter > ibc) ibc = counter + 1;
-    cmap[counter] = o;
-  }
-  uint64_t cib = 0;
-  if (!cmap.empty()) {
-    cib = cmap.begin()->second;
-    cmap.erase(cmap.begin());
-  }
-  K->h_key.assign(D, NOKEY);
-  K->h_ent.assign(D, NOENT);
-  K->h_xuid.assign(D, 0xFFFFFFFFu);
-  for (uint64_t o = 0; o < nb; ++o) {
-    memcpy(&K->ctr[o], &vol[(REG_BLOCKS + o) * 2048], 8);
-    const uint8_t* q = &vol[(REG_BLOCKS + o) * 2048 + 8];
-    for (uint64_t j = 0; j < DISK_ENTRIES; ++j, q += 10) {
-      uint16_t xu;
-      uint64_t h;
-      memcpy(&xu, q, 2);
-      memcpy(&h, q + 2, 8);
-      if (h == 0) continue;
-      K->h_key[o * DISK_ENTRIES + j] = h;
-      K->h_xuid[o * DISK_ENTRIES + j] = xu;
-    }
-  }
-  std::vector<std::unordered_map<uint64_t, uint64_t>> index(XUIDS);   // per xuid: hash -> slot
-  auto invalidate = [&](uint64_t b) {
-    if (K->ctr[b] == 0) return;
-    for (uint64_t i = b * DISK_ENTRIES; i < (b + 1) * DISK_ENTRIES; ++i) {
-      const uint32_t xu = K->h_xuid[i];
-      if (K->h_key[i] == NOKEY || xu >= XUIDS || K->uuid[xu].empty()) continue;
-      auto it = index[xu].find(K->h_key[i]);
-      if (it != index[xu].end() && it->second == i) index[xu].erase(it);
-    }
-  };
-  unsigned leading = CHECK_BOUNDARY;
-  while (!cmap.empty()) {
-    bool check;
-    if (leading != 0) {
-      check = true;
-      --leading;
-    } else {
-      check = cmap.size() <= CHECK_BOUNDARY;
-    }
-    const uint64_t b = cmap.begin()->second;
-    cmap.erase(cmap.begin());
-    for (uint64_t j = 0; j < DISK_ENTRIES; ++j) {
-      const uint64_t slot = b * DISK_ENTRIES + j;
-      const uint64_t h = K->h_key[slot];
-      const uint32_t xu = K->h_xuid[slot];
-      if (h == NOKEY || xu >= XUIDS || K->uuid[xu].empty()) continue;
-      index[xu].erase(h);                                   // ("Replacing previous cache entry.")
-      if (check && host_seg_hash(&K->h_data[slot * SEG]) != h) {
-        if (cib > b) {                                      // rewrite the block with errors
-          invalidate(b);
-          cib = b;
-          break;
-        }
-        continue;
-      }
-      index[xu][h] = slot;
-    }
-  }
-  for (uint32_t x = 1; x < XUIDS; ++x) {                    // registry_collect
-    if (K->uuid[x].empty() || !index[x].empty()) continue;
-    static const char zero36[36] = {0};
-    registry_write(K, x, zero36);
-    K->uuid[x].clear();
-  }
-  for (uint32_t x = 0; x < XUIDS; ++x)
-    for (const auto& kv : index[x]) {
-      const uint64_t slot = kv.second, b = slot / DISK_ENTRIES;
-      const uint64_t bn = nb + cib - ((cib + nb - b) % nb);
-      K->h_ent[slot] = DISK_ENTRIES * bn + slot % DISK_ENTRIES;
-    }
-  K->ibc = ibc == 0 ? 1 : ibc;
-  K->dclock = DISK_ENTRIES * (nb + cib);
-  K->pending = true;
-  return 0;
-}
-
 }  // namespace
 
 extern "C" {
-
-int xcg_disk_state_create(uint64_t disk_bytes, uint32_t flags, XcgDiskState** out) {
-  const uint64_t blocks = disk_bytes / SEG;
-  if (blocks <= 18) return -22;
-  const uint64_t nb = (blocks - 18) / (1 + DISK_ENTRIES);   // xcodec_cache_disk.cc:110-111
-  if (nb == 0 || nb * DISK_ENTRIES >= (1ull << 29)) return -22;
-  XcgDiskState* K = new XcgDiskState;
-  K->nb = nb;
-  K->D = (uint32_t)(nb * DISK_ENTRIES);
-  K->flags = flags;
-  K->bytes = disk_bytes;
-  K->ctr.assign(nb, 0);
-  K->reg.assign(18 * 2048, 0);
-  K->uuid.assign(1024, std::string());
-  *out = K;
-  return 0;
-}
-
-void xcg_disk_state_release(XcgDiskState* K) {
-  if (!K || --K->refs > 0) return;
-  K->mem.release_all();
-  if (K->dva) {
-    (void)hipDeviceSynchronize();
-    (void)hipMemUnmap(K->dva, K->pool_bytes);
-    (void)hipMemAddressFree(K->dva, K->pool_bytes);
-  }
-  if (K->vmm) (void)hipMemRelease(K->pool_h);
-  delete K;
-}
-
-void xcg_disk_state_stats(const XcgDiskState* K, uint64_t* st) {
-  uint64_t live = 0, fronts = 0;
-  for (const XcgPairState* f : K->fronts) fronts += f != nullptr;
-  if (K->device >= 0) {
-    DevMem mem;                    // (the probe word, freed on return)
-    uint32_t* d = nullptr;
-    uint32_t h = 0;
-    if (mem.dev(&d, 4) && hipMemset(d, 0, 4) == hipSuccess) {
-      hipLaunchKernelGGL(pair_count_live_kernel, dim3(grid_for(K->D)), dim3(256), 0, nullptr,
-                         (const uint64_t*)K->dent, (const uint32_t*)K->dxuid, K->D, (uint32_t)K->nb, K->dclock, NIL, d);
-      if (hipMemcpy(&h, d, 4, hipMemcpyDeviceToHost) == hipSuccess) live = h;
-    }
-  }
-  st[0] = live;
-  st[1] = K->dclock;
-  st[2] = K->nb;
-  st[3] = fronts;
-}
-
-// A pair front on disk K, on the current device.  Which front (xuid):
-//  * want_xuid >= 0: that one -- a host XCodecDiskCache's own xuid_, so the
-//    engine's fronts are the host disk's whatever order they bind in; uuid36,
-//    when given, must be registered there or nowhere;
-//  * uuid36: XCodecDisk::connect (xcodec_cache_disk.cc:640-690), the uuid's
-//    registered xuid, else the lowest xuid nothing holds (no registry entry, no
-//    front);
-//  * neither: XCodecDisk::local (:635-641), xuid 0 when it is registered and
-//    free (a reopened volume's local front), else the lowest free xuid under a
-//    generated UUID (registry_load's local UUID on a fresh volume, :575-596).
-// The registry entry is written once the front exists.
-void xcg_pair_state_set_unbounded(XcgPairState* P) { P->unbounded = true; }
-int xcg_pair_state_unbounded(const XcgPairState* P) { return P && P->unbounded ? 1 : 0; }
-
-int xcg_pair_state_create(uint32_t C, XcgDiskState* K, const char* uuid36, int want_xuid, XcgPairState** out) {
-  if (C == 0 || !K || (uint64_t)K->D + C >= (1ull << 30)) return -22;
-  if (uuid36 && (strlen(uuid36) != 36 || !uuid_ok((const uint8_t*)uuid36))) return -22;
-  if (want_xuid >= (int)XUIDS) return -22;
-  int device = 0;
-  if (hipGetDevice(&device) != hipSuccess) return -5;
-  auto bound = [&](uint32_t x) { return x < K->fronts.size() && K->fronts[x] != nullptr; };
-  uint32_t xuid = XUIDS;
-  if (uuid36)
-    for (uint32_t x = 0; x < XUIDS; ++x)
-      if (K->uuid[x] == uuid36) { xuid = x; break; }
-  if (want_xuid >= 0) {
-    if (xuid < XUIDS && xuid != (uint32_t)want_xuid) return -22;
-    xuid = (uint32_t)want_xuid;
-  } else if (!uuid36 && !K->uuid[0].empty() && !bound(0)) {
-    xuid = 0;
-  }
-  if (xuid < XUIDS && bound(xuid)) return -22;               // (one engine front per disk front)
-  if (xuid >= XUIDS)
-    for (xuid = 0; xuid < XUIDS && (bound(xuid) || !K->uuid[xuid].empty()); ++xuid) {
-    }
-  if (xuid >= XUIDS) return -22;                            // XCDFS_XUID_COUNT
-  char gen[37];
-  const char* name = uuid36;
-  if (!name && K->uuid[xuid].empty()) {
-    if (!gen_uuid(gen)) return -5;
-    name = gen;
-  }
-  const int brc = disk_bind(K, device);
-  if (brc) return brc;
-  XcgPairState* P = new XcgPairState;
-  P->C = C;
-  P->nb = (uint32_t)K->nb;
-  P->D = K->D;
-  P->disk = K;
-  P->xuid = (uint16_t)xuid;
-  P->gclock = K->dclock;
-  const uint64_t ids = (uint64_t)C + P->D;
-  auto fail = [&](int rc) {
-    unmap_pool(P);
-    P->mem.release_all();
-    delete P;
-    return rc;
-  };
-  DevMem& m = P->mem;
-  if (!(m.dev(&P->pkey, 8ull * C) && m.dev(&P->pdisk, 8ull * C) && m.dev(&P->lru, 4ull * C) &&
-        m.dev(&P->lru2, 4ull * C) && m.dev(&P->ptime, 8 * ids) && m.dev(&P->erep, 4 * ids)) ||
-      hipMemset(P->pkey, 0xFF, 8ull * C) != hipSuccess || hipMemset(P->pdisk, 0xFF, 8ull * C) != hipSuccess ||
-      hipMemset(P->ptime, 0xFF, 8 * ids) != hipSuccess || ensure_front_arrays(P) != 0 || map_pool(P, device) != 0)
-    return fail(-12);
-  uint8_t* blocks = P->pool + (uint64_t)C * SEG;
-  const uint64_t D = K->D;
-  if (!K->pending && !K->zeroed) {
-    if (hipMemset(blocks, 0, D * SEG) != hipSuccess) return fail(-5);
-    K->zeroed = K->vmm;
-  }
-  if (K->pending) {                                         // a reopened volume's ring and blocks
-    if (!K->ring_loaded &&
-        (hipMemcpy(K->dkey, K->h_key.data(), 8 * D, hipMemcpyHostToDevice) != hipSuccess ||
-         hipMemcpy(K->dent, K->h_ent.data(), 8 * D, hipMemcpyHostToDevice) != hipSuccess ||
-         hipMemcpy(K->dxuid, K->h_xuid.data(), 4 * D, hipMemcpyHostToDevice) != hipSuccess))
-      return fail(-5);
-    K->ring_loaded = true;
-    if (hipMemcpy(blocks, K->h_data.data(), D * SEG, hipMemcpyHostToDevice) != hipSuccess) return fail(-5);
-  }
-  if (!P->pool_vmm && !K->shadow_ok.empty()) {               // blocks of fronts that went away
-    for (uint64_t i = 0; i < D; ++i)
-      if (K->shadow_ok[i] &&
-          hipMemcpy(blocks + i * SEG, &K->shadow[i * SEG], SEG, hipMemcpyHostToDevice) != hipSuccess)
-        return fail(-5);
-  }
-  if (K->pending && K->vmm) {                                // (one copy serves every front)
-    K->pending = false;
-    K->zeroed = true;                                        // (the blocks hold the volume's bytes)
-    std::vector<uint64_t>().swap(K->h_key);
-    std::vector<uint64_t>().swap(K->h_ent);
-    std::vector<uint32_t>().swap(K->h_xuid);
-    std::vector<uint8_t>().swap(K->h_data);
-  }
-  if (name && K->uuid[xuid] != name) {
-    K->uuid[xuid] = std::string(name, 36);
-    registry_write(K, xuid, name);
-  }
-  P->gstale = true;                                          // (G from the disk's entries at the first call)
-  if (xuid >= K->fronts.size()) K->fronts.resize(xuid + 1, nullptr);
-  K->fronts[xuid] = P;
-  ++K->refs;
-  *out = P;
-  return 0;
-}
-
-// Where the write head is: XCodecDisk's current_index_block_ and
-// index_block_next_ (xcodec_cache_disk.cc:701-727).
-void xcg_disk_state_head(const XcgDiskState* K, uint64_t* index_block, uint64_t* next) {
-  *index_block = (K->dclock / DISK_ENTRIES) % K->nb;
-  *next = K->dclock % DISK_ENTRIES;
-}
-
-uint32_t xcg_pair_state_xuid(const XcgPairState* P) { return P->xuid; }
-
-// Write the volume as the reference's file stands now (registry, every
-// written index block with its counter and entries, the data blocks).
-namespace {
-
-struct OnDevice {                 // run on `dev`, restore the caller's device after
-  int prev = -1;
-  explicit OnDevice(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (dev >= 0 && prev != dev) (void)hipSetDevice(dev);
-  }
-  ~OnDevice() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
-// The disk's blocks through its own mapping of the physical allocation: the
-// bytes are there whether or not any front still maps them.
-int read_disk_blocks(const XcgDiskState* K, uint8_t* dst) {
-  const uint8_t* src = (const uint8_t*)K->dva;
-  for (const XcgPairState* f : K->fronts)            // (no mapping of its own: a live front's)
-    if (!src && f) src = f->pool + (uint64_t)f->C * SEG;
-  if (!src) return -5;
-  return hipMemcpy(dst, src, (size_t)K->D * SEG, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -5;
-}
-
-}  // namespace
-
-int xcg_disk_state_save(XcgDiskState* K, const char* path) {
-  const uint64_t nb = K->nb, D = K->D;
-  std::vector<uint64_t> key(D, NOKEY);
-  std::vector<uint32_t> xu(D, 0xFFFFFFFFu);
-  std::vector<uint8_t> data((size_t)D * SEG, 0);
-  if (K->pending && !K->ring_loaded) {
-    key = K->h_key;
-    xu = K->h_xuid;
-    data = K->h_data;
-  } else if (K->device >= 0) {
-    OnDevice on(K->device);
-    if (hipDeviceSynchronize() != hipSuccess ||
-        hipMemcpy(key.data(), K->dkey, 8 * D, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(xu.data(), K->dxuid, 4 * D, hipMemcpyDeviceToHost) != hipSuccess)
-      return -5;
-    if (K->vmm) {
-      if (read_disk_blocks(K, data.data())) return -5;
-    } else {
-      // per-front copies: a block comes from the live front that wrote it,
-      // else from what a front that went away left, else from the volume
-      if (!K->h_data.empty()) data = K->h_data;
-      for (uint64_t i = 0; i < D && !K->shadow_ok.empty(); ++i)
-        if (K->shadow_ok[i]) memcpy(&data[i * SEG], &K->shadow[i * SEG], SEG);
-      std::vector<uint8_t> tmp((size_t)D * SEG);
-      for (XcgPairState* f : K->fronts) {
-        if (!f) continue;
-        if (hipMemcpy(tmp.data(), f->pool + (uint64_t)f->C * SEG, D * SEG, hipMemcpyDeviceToHost) != hipSuccess)
-          return -5;
-        for (uint64_t i = 0; i < D; ++i)
-          if (xu[i] == f->xuid) memcpy(&data[i * SEG], &tmp[i * SEG], SEG);
-      }
-    }
-  }
-  const int fd = ::open(path, O_RDWR | O_CREAT | O_TRUNC, 0600);
-  if (fd == -1) return -2;
-  bool ok = ftruncate(fd, (off_t)K->bytes) == 0;
-  ok = ok && pwrite_all(fd, K->reg.data(), K->reg.size(), 0);
-  std::vector<uint8_t> ib(2048);
-  for (uint64_t b = 0; ok && b < nb; ++b) {
-    memset(ib.data(), 0, ib.size());
-    if (K->ctr[b] != 0) {
-      uint8_t* q = ib.data();
-      memcpy(q, &K->ctr[b], 8);
-      q += 8;
-      for (uint64_t j = 0; j < DISK_ENTRIES; ++j, q += 10) {
-        const uint64_t i = b * DISK_ENTRIES + j;
-        const uint64_t h = key[i] == NOKEY ? 0 : key[i];
-        const uint16_t x = h == 0 ? 0 : (uint16_t)xu[i];
-        memcpy(q, &x, 2);
-        memcpy(q + 2, &h, 8);
-      }
-    }
-    ok = pwrite_all(fd, ib.data(), 2048, (off_t)((REG_BLOCKS + b) * 2048));
-  }
-  ok = ok && pwrite_all(fd, data.data(), data.size(), (off_t)((REG_BLOCKS + nb) * 2048));
-  close(fd);
-  return ok ? 0 : -5;
-}
-
-// A volume read through an open descriptor (the reference's XCodecDisk keeps
-// its file open as fd_, xcodec_cache_disk.cc:840-871): reloaded when it holds
-// one (a non-empty file), else a fresh disk.
-int xcg_disk_state_open_fd(int fd, uint64_t disk_bytes, uint32_t flags, XcgDiskState** out) {
-  XcgDiskState* K = nullptr;
-  const int rc = xcg_disk_state_create(disk_bytes, flags, &K);
-  if (rc) return rc;
-  struct stat st;
-  if (fstat(fd, &st) != 0) {
-    delete K;
-    return -2;
-  }
-  if (st.st_size > 0 && load_volume(K, fd) != 0) {
-    delete K;
-    return -2;
-  }
-  *out = K;
-  return 0;
-}
-
-// Open a volume file: reloaded when it holds one, else a fresh disk.
-int xcg_disk_state_open(const char* path, uint64_t disk_bytes, uint32_t flags, XcgDiskState** out) {
-  const int fd = ::open(path, O_RDONLY);
-  if (fd == -1) {
-    if (errno == ENOENT) return xcg_disk_state_create(disk_bytes, flags, out);
-    return -2;
-  }
-  const int rc = xcg_disk_state_open_fd(fd, disk_bytes, flags, out);
-  close(fd);
-  return rc;
-}
-
-uint8_t* xcg_pair_state_pool(const XcgPairState* P) { return P->pool; }
-int xcg_disk_state_tier(const XcgDiskState* K) { return K->tier; }
-
-// A front goes away (its XCodecCache is deleted): its entries leave the ring's
-// index (XCodecDisk::disconnect).
-void xcg_pair_state_destroy(XcgPairState* P) {
-  if (!P) return;
-  XcgDiskState* K = P->disk;
-  (void)hipDeviceSynchronize();
-  if (K && K->dent && !P->pool_vmm) {                        // keep the blocks this front wrote
-    const uint64_t D = K->D;
-    std::vector<uint32_t> xu(D);
-    std::vector<uint8_t> tmp((size_t)D * SEG);
-    if (hipMemcpy(xu.data(), K->dxuid, 4 * D, hipMemcpyDeviceToHost) == hipSuccess &&
-        hipMemcpy(tmp.data(), P->pool + (uint64_t)P->C * SEG, D * SEG, hipMemcpyDeviceToHost) == hipSuccess) {
-      if (K->shadow_ok.empty()) {
-        K->shadow.assign((size_t)D * SEG, 0);
-        K->shadow_ok.assign(D, 0);
-      }
-      for (uint64_t i = 0; i < D; ++i)
-        if (xu[i] == P->xuid) {
-          memcpy(&K->shadow[i * SEG], &tmp[i * SEG], SEG);
-          K->shadow_ok[i] = 1;
-        }
-    }
-  }
-  if (K && K->dent)
-    hipLaunchKernelGGL(pair_drop_front_kernel, dim3(grid_for(K->D)), dim3(256), 0, nullptr, K->dkey, K->dent,
-                       (const uint32_t*)K->dxuid, K->D, (uint32_t)P->xuid);
-  (void)hipDeviceSynchronize();
-  unmap_pool(P);
-  P->mem.release_all();
-  if (K) {
-    K->fronts[P->xuid] = nullptr;
-    xcg_disk_state_release(K);
-  }
-  delete P;
-}
-
-// Drop everything this front holds (XCodecCache objects have no clear: this is
-// a fresh front; on a disk of its own, a fresh volume).  The caller wipes G.
-int xcg_pair_state_clear(XcgPairState* P) {
-  XcgDiskState* K = P->disk;
-  uint64_t others = 0;
-  for (const XcgPairState* f : K->fronts) others += f && f != P;
-  if (hipMemset(P->pkey, 0xFF, 8ull * P->C) != hipSuccess || hipMemset(P->pdisk, 0xFF, 8ull * P->C) != hipSuccess)
-    return -5;
-  hipLaunchKernelGGL(pair_drop_front_kernel, dim3(grid_for(K->D)), dim3(256), 0, nullptr, K->dkey, K->dent,
-                     (const uint32_t*)K->dxuid, K->D, others ? (uint32_t)P->xuid : NIL);
-  if (!others) {                                             // a fresh volume
-    K->dclock = 0;
-    K->ctr.assign(K->nb, 0);
-    K->ibc = 1;
-  }
-  P->pcount = 0;
-  P->gclock = K->dclock;
-  P->gstale = false;
-  P->prev_passes = 1;
-  return hipDeviceSynchronize() == hipSuccess ? 0 : -5;
-}
-
-void xcg_pair_state_stats(const XcgPairState* P, uint64_t* st) {
-  const XcgDiskState* K = P->disk;
-  DevMem mem;                      // (the probe word, freed on return)
-  uint32_t h = 0;
-  uint32_t* d = nullptr;
-  if (mem.dev(&d, 4) && hipMemset(d, 0, 4) == hipSuccess) {
-    hipLaunchKernelGGL(pair_count_live_kernel, dim3(grid_for(K->D)), dim3(256), 0, nullptr, (const uint64_t*)K->dent,
-                       (const uint32_t*)K->dxuid, K->D, (uint32_t)K->nb, K->dclock, (uint32_t)P->xuid, d);
-    (void)hipMemcpy(&h, d, 4, hipMemcpyDeviceToHost);
-  }
-  st[0] = P->pcount;
-  st[1] = h;
-  st[2] = K->dclock;
-  st[3] = P->nb;
-}
-
-uint32_t xcg_pair_state_last_base(const XcgPairState* P) { return P->last_base; }
-uint32_t xcg_pair_state_limit(const XcgPairState* P) { return P->C; }
-uint32_t xcg_pair_state_disk_blocks(const XcgPairState* P) { return P->D; }
-XcgDiskState* xcg_pair_state_disk(const XcgPairState* P) { return P->disk; }
-const uint64_t* xcg_pair_state_ptime(const XcgPairState* P) { return P->ptime; }
 
 int xcg_pair_sync(XcgPairState* P, const PairGpu* G, hipStream_t st) { return pair_sync_front(P, *G, st); }
 
@@ -2518,7 +1566,7 @@ int xcg_pair_encode_stream(const XcgStreamArgs* a0, XcgPairState* P, int* rounds
     if (pair_debug())
       fprintf(stderr, "pair: ms seed %.2f seed-replay %.2f parse %.2f replay %.2f commit %.2f (primary %u, clock %llu)\n",
               ms(t0, t1), ms(t1, t2), t_parse, t_replay, ms(t3, clk::now()), P->pcount,
-              (unsigned long long)P->disk->dclock);
+              (unsigned long long)P->disk->vol.dclock);
     // the next sub-batch starts with every hash visible to its end
     if (fill_ptime(P, st)) return -5;
     P->last_base = i0;
