@@ -1,7 +1,7 @@
 """Calls of one context on different HIP streams are serialised as the
 reference's calls on one cache are (one event thread): the context records
 its completion marker behind its last call only when another stream or a host
-wait needs it (xcg_api.hip ctx_flush_mark / ctx_order).  A second batch issued
+wait needs it (xcg_ctx.hip ctx_flush_mark / ctx_order).  A second batch issued
 on another stream right behind the first must see every segment the first one
 committed, and a cache clear between repetitions orders against both.  (The
 stream encode's own host waits -- on its verification flags -- already order

@@ -66,7 +66,7 @@ def test_engine_reproduces_reference(E, golden_pipe, name):
 def test_engine_over_unknown_capacity(E, golden_pipe):
     """65,537 distinct unknown hashes in one decode.  The reference sends 129
     <ASK> ops.  The engine's unknown-hash set holds 65,536 (UNKNOWN_CAP,
-    xcg_api.hip): it either matches the reference or fails loudly with
+    xcg_ctx.h): it either matches the reference or fails loudly with
     XCG_EOVERFLOW, nothing produced and nothing entered into the cache
     (Known departures)."""
     from wanproxy_amd.xcgpu import XCG_EOVERFLOW, XCGError

@@ -1,7 +1,7 @@
 // The library's internal interface: every struct and every extern "C" function
 // that crosses translation units inside libxcgpu (the host ABI layer
-// xcg_api.hip, xcg_pipe.cpp and the kernel drivers xcg_encode_* / xcg_decode /
-// xcg_lru / xcg_pair / xcg_hash).  The file that defines one of these functions
+// xcg_ctx.hip and xcg_api_*.hip, xcg_pipe.cpp and the kernel drivers
+// xcg_encode_* / xcg_decode / xcg_lru / xcg_pair / xcg_hash).  The file that defines one of these functions
 // and every file that calls it include this header, so a prototype that drifts
 // is a compile error.  Plain data only: xcg_pipe.cpp compiles it as host C++.
 //
@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "xcg_devmem.h"
+#include "xcg_rc.h"      // the drivers' return codes (XCG_RC_*)
 
 struct xcg_ctx;
 
@@ -31,9 +32,81 @@ struct XcgCacheView {
   uint32_t gmask = 0;
 };
 
+// A context's batch scratch (allocated by ensure_scratch, xcg_ctx.hip): every
+// array a stream batch works in, declared here once.  The stream driver's
+// arguments below begin with a copy of it.
+struct XcgBatchScratch {
+  uint32_t n_cap = 0, maxd_cap = 0;   // chunks / declaration rows per chunk the scratch was grown for
+  uint64_t* b_keys = nullptr;
+  uint64_t* b_vals = nullptr;
+  uint32_t b_mask = 0;
+  uint32_t* r_filt = nullptr;
+  uint32_t* r_ftab = nullptr;
+  void* decl = nullptr;             // uint4 rows
+  uint32_t* ndecl = nullptr;
+  uint32_t* changed = nullptr;
+  uint32_t* h_changed = nullptr;    // pinned host word
+  uint32_t* r_gfilt = nullptr;      // the round's copy of the cache's global lane filter
+  uint32_t* bcount = nullptr;       // [64]
+  // verification: a second batch table (tables alternate between rounds, same
+  // mask), the changed-hash table (hash -> chunk range), per-chunk batch hits, flags
+  uint64_t* b2_keys = nullptr;
+  uint64_t* b2_vals = nullptr;
+  uint64_t* r_keys = nullptr;
+  uint64_t* r_vals = nullptr;
+  uint32_t r_mask = 0;
+  uint64_t* hits = nullptr;         // n_cap * maxh batch hits
+  uint32_t* nhits = nullptr;
+  uint32_t maxh = 0;
+  uint32_t* need = nullptr;
+  uint32_t* vflags = nullptr;       // [0] a_first, [1] any, [2] declarations in the last table built
+  uint32_t* h_vflags = nullptr;     // pinned
+  // verification (a), exactly (verify_probe_kernel): the hashes that became
+  // visible to more chunks -> that chunk range, and their Bloom words
+  uint64_t* a_keys = nullptr;       // [XCG_VERIFY_A_CAP]
+  uint64_t* a_vals = nullptr;
+  uint32_t* a_bits = nullptr;       // [XCG_VERIFY_A_WORDS]
+  // the quiet-chunk screen (small chunks): the 128 KiB LDS fold of the round's
+  // global lane filter, and the work list of chunks it sends to the parse
+  // ([0] count, [1..n] chunks); null: no screen
+  uint32_t* s_fold = nullptr;
+  uint32_t* s_work = nullptr;
+  uint32_t* s_info = nullptr;       // [n] the screen's verdict per chunk
+  void* s_rows = nullptr;           // [n * 4] uint4: its staged rows
+  uint32_t* s_qcnt = nullptr;       // [n] and [n * 1024]: the windows it queues for the probe
+  uint32_t* s_qkeys = nullptr;
+  uint32_t last_maxd = 0;           // declaration stride of the last stream batch
+  // bounded (LRU) cache and pair only (null / 0 on other contexts): every
+  // chunk's cache references (xcg_lru.hip)
+  void* ev = nullptr;               // n_cap * maxe uint4
+  uint32_t* nev = nullptr;
+  uint32_t maxe = 0;
+  uint32_t* ev_base = nullptr;      // [n + 1], [n + 1]: the LRU pass's row and enter bases
+  uint32_t* enter_base = nullptr;
+  uint32_t* ev_slot = nullptr;      // [n * maxe]: each reference's pool slot / LRU time
+  uint64_t* ev_time = nullptr;
+  // re-parse restart (xcg_encode_wave.h RestartArgs): output length after each
+  // REF-making lookup, per chunk the earliest / latest contradicted lookup
+  // time, and the backup of the previous pass's rows of the flagged chunks
+  uint32_t* eo = nullptr;           // [n * maxe]
+  uint32_t* bad_t = nullptr;        // [n] (~0: none)
+  uint32_t* bad_hi = nullptr;       // [n]
+  uint32_t* bslot = nullptr;        // [n]
+  uint32_t* b_count = nullptr;      // [1]
+  uint32_t b_slots = 0;
+  void* b_ev = nullptr;             // [b_slots * maxe] uint4
+  uint32_t* b_eo = nullptr;         // [b_slots * maxe]
+  uint64_t* b_hits = nullptr;       // [b_slots * maxh]
+  uint32_t* b_cnt = nullptr;        // [b_slots * 4]
+  uint8_t* b_out = nullptr;         // [b_slots * b_stride]
+  uint64_t b_stride = 0;
+  void* splice = nullptr;           // [n] uint4
+};
+
 // Arguments of the stream-semantics encode driver (xcg_launch_encode_stream),
-// and of the bounded-cache and pair passes around it.
-struct XcgStreamArgs {
+// and of the bounded-cache and pair passes around it: the context's batch
+// scratch and the call.
+struct XcgStreamArgs : XcgBatchScratch {
   const uint8_t* in;
   const uint64_t* chunk_off;
   const uint32_t* chunk_len;
@@ -45,81 +118,19 @@ struct XcgStreamArgs {
   uint32_t* stats;
   int32_t* status;
   XcgCacheView g;        // persistent cache
-  // batch scratch
-  uint64_t* b_keys;
-  uint64_t* b_vals;
-  uint32_t b_mask;
-  uint32_t* r_filt;
-  uint32_t* r_ftab;
-  void* decl;             // uint4 rows
-  uint32_t* ndecl;
-  uint32_t maxd;
-  uint32_t* changed;
-  uint32_t* h_changed;   // pinned host word
-  uint32_t* r_gfilt;     // the round's copy of the cache's global lane filter
-  uint32_t* bcount;      // [64]
-  // verification: a second batch table (tables alternate between rounds), the
-  // changed-hash table, per-chunk batch hits, flags
-  uint64_t* b2_keys;
-  uint64_t* b2_vals;
-  uint64_t* r_keys;
-  uint64_t* r_vals;
-  uint32_t r_mask;
-  uint64_t* hits;
-  uint32_t* nhits;
-  uint32_t maxh;
-  uint32_t* need;
-  uint32_t* vflags;      // [0] a_first, [1] any, [2] declarations in the last table built
-  uint32_t* h_vflags;    // pinned
+  uint32_t maxd;         // the call's declaration stride (<= maxd_cap)
   int seed;              // start from the tiling seed instead of round 0
   uint32_t* decls_out;   // (host) declarations the batch made, ~0 if unknown
-  // bounded (LRU) cache: eviction times per pool slot, the reference lists,
-  // and whether the driver commits (the LRU pass commits itself)
+  // bounded (LRU) cache: eviction times per pool slot, and whether the driver
+  // commits (the LRU pass commits itself)
   const uint64_t* ptime;
-  void* ev;
-  uint32_t* nev;
-  uint32_t maxe;
-  uint32_t* ev_base;     // [n + 1], [n + 1]: the LRU pass's row and enter bases
-  uint32_t* enter_base;
-  uint32_t* ev_slot;     // [n * maxe]: each reference's pool slot / LRU time
-  uint64_t* ev_time;
   int no_commit;
   int keep_decls;        // start from the declaration lists already in decl/ndecl
   int need_given;        // (keep_decls) round 1 parses only the chunks flagged in need[]
-  // re-parse restart (bounded / pair): output length after each REF-making
-  // lookup, per chunk the earliest / latest contradicted lookup time, and the
-  // backup of the previous pass's rows of the flagged chunks
-  uint32_t* eo;          // [n * maxe]
-  uint32_t* bad_t;       // [n] (~0: none)
-  uint32_t* bad_hi;      // [n]
   int restart;           // (need_given) round 1 resumes flagged chunks from their rows
-  uint32_t* bslot;       // [n]
-  uint32_t* b_count;     // [1]
-  uint32_t b_slots;
-  void* b_ev;            // [b_slots * maxe] uint4
-  uint32_t* b_eo;        // [b_slots * maxe]
-  uint64_t* b_hits;      // [b_slots * maxh]
-  uint32_t* b_cnt;       // [b_slots * 4]
-  uint8_t* b_out;        // [b_slots * b_stride]
-  uint64_t b_stride;
-  void* splice;          // [n] uint4
-  // verification (a), exactly (verify_probe_kernel): the hashes that became
-  // visible to more chunks -> that chunk range, and their Bloom words
-  uint64_t* a_keys;      // [XCG_VERIFY_A_CAP]
-  uint64_t* a_vals;
-  uint32_t* a_bits;      // [XCG_VERIFY_A_WORDS]
   // the context's event behind the verification flags' copy (hipEvent_t; null:
   // the driver makes one for the call)
   void* flags_ev;
-  // the quiet-chunk screen (small chunks): the 128 KiB LDS fold of the round's
-  // global lane filter, and the work list of chunks it sends to the parse
-  // ([0] count, [1..n] chunks); null: no screen
-  uint32_t* s_fold;
-  uint32_t* s_work;
-  uint32_t* s_info;    // [n] the screen's verdict per chunk
-  void* s_rows;        // [n * 4] uint4: its staged rows
-  uint32_t* s_qcnt;    // [n] and [n * 1024]: the windows it queues for the probe
-  uint32_t* s_qkeys;
   // (bounded cache) called behind each Jacobi verification, before the host
   // reads its flags: queues work gated on vflags[1] == 0 (the round converged)
   int (*post_verify)(void* user, const uint32_t* vbusy, hipStream_t st);
@@ -229,8 +240,35 @@ extern "C" uint8_t* xcg_pair_state_pool(const XcgPairState* P);
 extern "C" int xcg_pair_decode_commit(XcgPairState* P, const PairGpu* G, hipStream_t st);
 
 
-// Arguments of the batch decode driver (xcg_launch_decode).
-struct XcgDecodeArgs {
+// A context's decode scratch (allocated by ensure_dscratch / ensure_dchunks,
+// xcg_ctx.hip), declared here once; the batch decode driver's arguments begin
+// with a copy of it.
+struct XcgDecodeScratch {
+  uint32_t x_cap = 0;
+  uint64_t* x_keys = nullptr;
+  uint64_t* x_vals = nullptr;
+  uint64_t* x_latest = nullptr;
+  // name reuse: parallel to x_vals the EXTRACT that claimed each slot and the differing-bytes flags; the
+  // duplicate EXTRACT list (the later EXTRACTs of a hash; x_cap / 2 >= every EXTRACT of a batch)
+  uint64_t* x_owner = nullptr;
+  uint32_t* x_flag = nullptr;
+  uint32_t* dup_slot = nullptr;
+  uint64_t* dup_pos = nullptr;
+  uint64_t* u_keys = nullptr;      // unknown-hash set, 2 * unknown_cap slots
+  uint64_t* unknown = nullptr;
+  uint64_t* unknown_pos = nullptr;
+  uint32_t* nunknown = nullptr;    // 4 words: [0] unknown hashes, [1] hashes whose EXTRACTs differ, [2] their occurrences
+  uint64_t* scratch = nullptr;     // [0] total out, [1] REF block, [2] BACKREF error, [3] duplicate EXTRACTs - 1, [4] declares,
+                                   // [5] BACKREFs, [6] t_end
+  uint64_t* h_scratch = nullptr;   // pinned copy of scratch[0..5], [6] nunknown | flagged hashes << 32, [12..14] reuse stats
+  uint32_t chunk_cap = 0;
+  uint64_t* chunk_tmp = nullptr;   // 4 * n u64: n_decl, n_bref, decl_base, n_decl_emit
+  uint4* d_tail = nullptr;         // 256 declare records (window update)
+};
+
+// Arguments of the batch decode driver (xcg_launch_decode): the context's
+// decode scratch and the call.
+struct XcgDecodeArgs : XcgDecodeScratch {
   const uint8_t* in;
   const uint64_t* chunk_off;
   const uint32_t* chunk_len;
@@ -243,20 +281,8 @@ struct XcgDecodeArgs {
   uint64_t* consumed;
   int32_t* status;
   XcgCacheView g;        // persistent cache
-  uint64_t* x_keys;
-  uint64_t* x_vals;
-  uint64_t* x_latest;
-  uint32_t x_mask;
-  uint64_t* u_keys;      // unknown-hash set, 2 * unknown_cap slots
-  uint64_t* unknown;
-  uint64_t* unknown_pos;
-  uint32_t* nunknown;    // 4 words: [0] unknown hashes, [1] hashes whose EXTRACTs differ, [2] their occurrences
+  uint32_t x_mask;       // x_cap - 1
   uint32_t unknown_cap;
-  uint64_t* scratch;     // [0] total out, [1] REF block, [2] BACKREF error, [3] duplicate EXTRACTs - 1, [4] declares,
-                         // [5] BACKREFs, [6] t_end
-  uint64_t* h_scratch;   // pinned copy of scratch[0..5], [6] nunknown | flagged hashes << 32, [12..14] reuse stats
-  uint64_t* chunk_tmp;   // 4 * n u64: n_decl, n_bref, decl_base, n_decl_emit
-  uint4* d_tail;         // 256 declare records
   uint64_t* win_hash;    // the decoder's BACKREF window
   uint8_t* win_seg;
   uint64_t win_count;
@@ -264,12 +290,7 @@ struct XcgDecodeArgs {
   uint32_t maxd;         // EXTRACTs a chunk can hold (bounded: declaration rows per chunk)
   XcgPairState* pair;    // XCodecCachePair (null: not a pair)
   int no_window;         // the BACKREF window is left alone (<LEARN>, single-segment host calls)
-  // name reuse: parallel to x_vals (owner, flag); the duplicate EXTRACT list
-  uint64_t* x_owner;
-  uint32_t* x_flag;
-  uint32_t* dup_slot;
-  uint64_t* dup_pos;
-  uint32_t dup_cap;
+  uint32_t dup_cap;      // x_cap / 2
 };
 
 // Arguments of the independent decode driver (xcg_launch_decode_independent):
@@ -378,7 +399,7 @@ extern "C" uint32_t xcg_decode_small_res_words(void);
 extern "C" uint32_t xcg_decode_small_phases(void);
 extern "C" uint32_t xcg_decode_small_lds_in(void);
 
-// (xcg_api.hip for xcg_pipe.cpp) a connecting pipe takes and drops its registry context
+// (xcg_ctx.hip for xcg_pipe.cpp) a connecting pipe takes and drops its registry context
 // (connect_hold: xcg_ctx_connect with the hold taken under the registry lock)
 extern "C" int xcg_ctx_connect_hold(xcg_ctx* parent, const char* uuid36, xcg_ctx** out);
 extern "C" void xcg_registry_release(xcg_ctx* c);

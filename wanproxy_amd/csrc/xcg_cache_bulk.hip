@@ -328,8 +328,8 @@ size_t sort_temp_bytes(uint64_t m) {
 
 }  // namespace
 
-// Learn a->n segments in order.  0; -75: an unbounded cache would have to hold
-// more than its capacity (nothing written); -12; -5.  Asynchronous on a
+// Learn a->n segments in order.  0; XCG_RC_OVERFLOW: an unbounded cache would have to hold
+// more than its capacity (nothing written); XCG_RC_NOMEM; XCG_RC_HIP.  Asynchronous on a
 // bounded cache; an unbounded one synchronises `st` once (the gate's verdict).
 extern "C" int xcg_bulk_learn(const XcgBulkLearn* a, hipStream_t st) {
   using namespace xcg;
@@ -358,7 +358,7 @@ extern "C" int xcg_bulk_learn(const XcgBulkLearn* a, hipStream_t st) {
       v1 = cv.take<uint32_t>(items);
       sort_tmp = cv.take<uint8_t>(sort_bytes);
     }
-    if (pass == 0 && !tmp.alloc(&cv.base, cv.off)) return -12;
+    if (pass == 0 && !tmp.alloc(&cv.base, cv.off)) return XCG_RC_NOMEM;
   }
   const HashTab b{bkeys, bvals, (uint32_t)(bcap - 1)}, g = tab_of(a->g);
   const FiltSet fs = filters_of(a->g);
@@ -377,14 +377,15 @@ extern "C" int xcg_bulk_learn(const XcgBulkLearn* a, hipStream_t st) {
     if (hipGetLastError() != hipSuccess ||
         hipMemcpyAsync(&gate, cnt + N_GATE, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)
-      return -5;
-    return gate ? -75 : 0;
+      return XCG_RC_HIP;
+    return gate ? XCG_RC_OVERFLOW : 0;
   }
   const unsigned cg = grid_for(C) < 1024 ? grid_for(C) : 1024;
   hipLaunchKernelGGL(bulk_items_kernel, dim3(grid_for(items)), blk, 0, st, n, C, (const uint32_t*)a->g.nseg,
                      (const uint32_t*)L->queue, (const uint64_t*)L->lastref, (const uint32_t*)slot, L->clock, k0, v0);
   size_t sb = sort_bytes;
-  if (rocprim::radix_sort_pairs(sort_tmp, sb, k0, k1, v0, v1, (size_t)items, 0, 64, st) != hipSuccess) return -5;
+  if (rocprim::radix_sort_pairs(sort_tmp, sb, k0, k1, v0, v1, (size_t)items, 0, 64, st) != hipSuccess)
+    return XCG_RC_HIP;
   hipLaunchKernelGGL(bulk_plan_kernel, dim3(1), dim3(64), 0, st, C, a->g.nseg, cnt);
   hipLaunchKernelGGL(bulk_zero32_kernel, dim3(cg), blk, 0, st, L->alive, C);
   hipLaunchKernelGGL(bulk_keep_kernel, dim3(grid_for(items)), blk, 0, st, C, (const uint32_t*)cnt,
@@ -396,7 +397,7 @@ extern "C" int xcg_bulk_learn(const XcgBulkLearn* a, hipStream_t st) {
   hipLaunchKernelGGL(bulk_copy_kernel, waves, blk, 0, st, a->segs, n, (const uint32_t*)slot, (const uint32_t*)cnt,
                      a->g.pool, (const uint32_t*)L->alive);
   // G and its filters again from the live slots: an open-addressed table has no delete
-  if (hipGetLastError() != hipSuccess || xcg_lru_rebuild_table(&a->g, L, a->status, st)) return -5;
+  if (hipGetLastError() != hipSuccess || xcg_lru_rebuild_table(&a->g, L, a->status, st)) return XCG_RC_HIP;
   // the host side of the commit, as xcg_lru_commit's: the new order, and a
   // clock above every time the batch gave out (clock + i, i < n)
   uint32_t* q = L->queue;
@@ -416,7 +417,7 @@ extern "C" int xcg_bulk_export(const XcgCacheView* gv, const XcgLruState* L, uin
   if (L) {
     hipLaunchKernelGGL(bulk_gather_kernel, waves, blk, 0, st, live, (const uint32_t*)L->queue,
                        (const uint64_t*)nullptr, (const uint64_t*)L->skey, (const uint8_t*)gv->pool, d_segs, d_hash);
-    return hipGetLastError() == hipSuccess ? 0 : -5;
+    return hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
   }
   const size_t sort_bytes = sort_temp_bytes(live);
   StreamTemp tmp(st);
@@ -432,14 +433,14 @@ extern "C" int xcg_bulk_export(const XcgCacheView* gv, const XcgLruState* L, uin
     v1 = cv.take<uint32_t>(live);
     cnt = cv.take<uint32_t>(N_WORDS);
     sort_tmp = cv.take<uint8_t>(sort_bytes);
-    if (pass == 0 && !tmp.alloc(&cv.base, cv.off)) return -12;
+    if (pass == 0 && !tmp.alloc(&cv.base, cv.off)) return XCG_RC_NOMEM;
   }
   const HashTab g = tab_of(*gv);
-  if (hipMemsetAsync(cnt, 0, 4 * N_WORDS, st) != hipSuccess) return -5;
+  if (hipMemsetAsync(cnt, 0, 4 * N_WORDS, st) != hipSuccess) return XCG_RC_HIP;
   hipLaunchKernelGGL(bulk_compact_kernel, dim3(grid_for((uint64_t)g.mask + 1)), blk, 0, st, g, live, k0, v0, cnt);
   size_t sb = sort_bytes;
-  if (rocprim::radix_sort_pairs(sort_tmp, sb, k0, k1, v0, v1, (size_t)live, 0, 64, st) != hipSuccess) return -5;
+  if (rocprim::radix_sort_pairs(sort_tmp, sb, k0, k1, v0, v1, (size_t)live, 0, 64, st) != hipSuccess) return XCG_RC_HIP;
   hipLaunchKernelGGL(bulk_gather_kernel, waves, blk, 0, st, live, (const uint32_t*)v1, (const uint64_t*)k1,
                      (const uint64_t*)nullptr, (const uint8_t*)gv->pool, d_segs, d_hash);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
 }

@@ -1497,14 +1497,14 @@ extern "C" int xcg_launch_cache_lookup(const XcgCacheView* g, uint64_t key, uint
                                        hipStream_t s) {
   hipLaunchKernelGGL(xcg::cache_lookup_kernel, dim3(1), dim3(64), 0, s, xcg::tab_of(*g), (const uint8_t*)g->pool, key,
                      seg_out, found);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
 }
 
 extern "C" int xcg_launch_cache_enter(const XcgCacheView* g, uint64_t key, const uint8_t* seg, int replace_only,
                                       int32_t* result, hipStream_t s) {
   hipLaunchKernelGGL(xcg::cache_enter_kernel, dim3(1), dim3(64), 0, s, xcg::tab_of(*g), g->pool, g->nseg, g->seg_cap,
                      xcg::filters_of(*g), key, seg, replace_only, result);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
 }
 
 extern "C" int xcg_launch_pack(const uint8_t* src, const uint64_t* src_off, const uint64_t* len, uint32_t n,
@@ -1514,10 +1514,10 @@ extern "C" int xcg_launch_pack(const uint8_t* src, const uint64_t* src_off, cons
   hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, stream, len, dst_off, n, d_total);
   hipLaunchKernelGGL(pack_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, src, src_off, len, (const uint64_t*)dst_off,
                      dst, n);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
 }
 
-// Returns 0, -75 (output too small) or -5.  Outputs: total decoded bytes, the
+// Returns 0, XCG_RC_OVERFLOW (output too small) or XCG_RC_HIP.  Outputs: total decoded bytes, the
 // REF block and BACKREF error positions (~0 = none), unknown-REF count.
 // Diagnostics (bench.py's decode roofline): HIP events bracket the batch
 // decode's three device segments on its stream -- scan, refcheck / sizing,
@@ -1636,7 +1636,7 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
       hipMemsetAsync(a->scratch + 1, 0xFF, 24, stream) != hipSuccess ||      // (stop positions, duplicate count - 1)
       hipMemsetAsync(a->nunknown, 0, 16, stream) != hipSuccess ||
       hipMemsetAsync(a->u_keys, 0xFF, 16ull * a->unknown_cap, stream) != hipSuccess)
-    return -5;
+    return XCG_RC_HIP;
   // scan, then number the declares
   hipLaunchKernelGGL(decode_kernel<false>, grid, block, 0, stream, p);
   hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, stream, (const uint64_t*)p.n_decl,
@@ -1646,15 +1646,15 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
   seg1.end();
   if (hipMemcpyAsync(a->h_scratch + 3, a->scratch + 3, 24, hipMemcpyDeviceToHost, stream) != hipSuccess ||
       hipStreamSynchronize(stream) != hipSuccess)
-    return -5;
+    return XCG_RC_HIP;
   const uint64_t ndup = a->h_scratch[3] + 1u, ndecl = a->h_scratch[4], nbref = a->h_scratch[5];
   // Duplicate EXTRACTs (rare; none in an encoder's stream on a fresh cache):
   // compare each with its hash's owner and flag the hashes whose bytes differ.
   // The count of flagged hashes comes back with the sizing pass's readback.
-  if (ndup > a->dup_cap) return -5;                  // (the list holds every EXTRACT the batch can have)
+  if (ndup > a->dup_cap) return XCG_RC_HIP;                  // (the list holds every EXTRACT the batch can have)
   a->h_scratch[12] = ndup;
   if (ndup) {
-    if (hipMemsetAsync(a->x_flag, 0, 4ull * (a->x_mask + 1), stream) != hipSuccess) return -5;
+    if (hipMemsetAsync(a->x_flag, 0, 4ull * (a->x_mask + 1), stream) != hipSuccess) return XCG_RC_HIP;
     hipLaunchKernelGGL(dec_dup_kernel, dim3((unsigned)((ndup + 3) / 4)), dim3(256), 0, stream, p, (uint32_t)ndup,
                        a->lru != nullptr || a->pair != nullptr);
   }
@@ -1666,13 +1666,13 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
   LruBatch lb{};
   uint4 *raw = nullptr, *evs = nullptr;
   if (a->lru) {
-    if (nbref > 0) return -95;                       // (BACKREF stop points are not modelled on a bounded cache)
+    if (nbref > 0) return XCG_RC_NOTSUP;             // (BACKREF stop points are not modelled on a bounded cache)
     XcgLruState* L = a->lru;
     const uint64_t m = ndecl ? ndecl : 1;
     // raw ops, classified ops, declaration rows | evtime | evslot, per-chunk
     // counts, bases, flags
     const uint64_t bytes = 32 * m + 16ull * n * a->maxd + 8 * m + 4 * m + 20ull * (n + 1) + 64;
-    if (!lru_tmp.alloc(&lru_mem, bytes)) return -5;
+    if (!lru_tmp.alloc(&lru_mem, bytes)) return XCG_RC_HIP;
     raw = (uint4*)lru_mem;
     evs = raw + m;
     uint4* drow = evs + m;
@@ -1693,22 +1693,22 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
     lb.status = a->status;
     lb.ev_bound = m;
     hipLaunchKernelGGL(dec_ops_kernel, grid, block, 0, stream, p, raw);
-    if (xcg_lru_reset_times(L, stream)) return -5;
+    if (xcg_lru_reset_times(L, stream)) return XCG_RC_HIP;
     p.ptime = L->ptime;
     uint64_t blockp = ~0ull;
     bool agreed = false;
     for (int pass = 0; pass < 64 && !agreed; ++pass) {
       if (hipMemsetAsync(blk, 0xFF, 8, stream) != hipSuccess || hipMemsetAsync(changes, 0, 4, stream) != hipSuccess)
-        return -5;
+        return XCG_RC_HIP;
       hipLaunchKernelGGL(dec_classify_kernel<false>, grid, block, 0, stream, p, (const uint4*)raw, evs, nev32, drow, nd32,
                          a->maxd, blockp, blk, changes, pass == 0 ? 1 : 0);
-      if (xcg_lru_times(&lb, L, stream)) return -5;   // (synchronises)
+      if (xcg_lru_times(&lb, L, stream)) return XCG_RC_HIP;   // (synchronises)
       if (hipMemcpyAsync(a->h_scratch + 8, blk, 16, hipMemcpyDeviceToHost, stream) != hipSuccess ||
           hipStreamSynchronize(stream) != hipSuccess)
-        return -5;
+        return XCG_RC_HIP;
       const uint64_t nb = a->h_scratch[8];
       const uint32_t nchg = (uint32_t)a->h_scratch[9];
-      if ((uint64_t)L->h_tot[1] + L->h_tot[8] > L->C) return -95;   // enters + persistent lookups > limit
+      if ((uint64_t)L->h_tot[1] + L->h_tot[8] > L->C) return XCG_RC_NOTSUP;   // enters + persistent lookups > limit
       if (getenv("XCG_LRU_DEBUG"))
         fprintf(stderr, "lru-dec: n %u pass %d enters %u evict %u live %u hits %u changes %u block %llx -> %llx\n", n,
                 pass, L->h_tot[1], L->h_tot[2], L->h_tot[3], L->h_tot[8], nchg, (unsigned long long)blockp,
@@ -1716,7 +1716,7 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
       agreed = nchg == 0 && nb == blockp;
       blockp = nb;
     }
-    if (!agreed) return -75;
+    if (!agreed) return XCG_RC_OVERFLOW;
   }
   // Pair: classify every op against ptime (the time a hash leaves both
   // levels), replay the classified ops through the pair's policy on the host
@@ -1725,11 +1725,11 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
   uint8_t* pair_mem = nullptr;
   uint4* prow = nullptr;
   if (a->pair) {
-    if (nbref > 0) return -95;                       // (BACKREF stop points are not modelled on a pair)
-    if (xcg_pair_decode_begin(a->pair, stream)) return -5;
+    if (nbref > 0) return XCG_RC_NOTSUP;                       // (BACKREF stop points are not modelled on a pair)
+    if (xcg_pair_decode_begin(a->pair, stream)) return XCG_RC_HIP;
     const uint64_t m = ndecl ? ndecl : 1;
     const uint64_t bytes = 32 * m + 16ull * n * a->maxd + 8ull * (n + 1) + 64;
-    if (!pair_tmp.alloc(&pair_mem, bytes)) return -5;
+    if (!pair_tmp.alloc(&pair_mem, bytes)) return XCG_RC_HIP;
     raw = (uint4*)pair_mem;
     evs = raw + m;
     prow = evs + m;
@@ -1743,10 +1743,10 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
     bool agreed = false;
     for (int pass = 0; pass < 64 && !agreed; ++pass) {
       if (hipMemsetAsync(blk, 0xFF, 8, stream) != hipSuccess || hipMemsetAsync(changes, 0, 4, stream) != hipSuccess)
-        return -5;
+        return XCG_RC_HIP;
       hipLaunchKernelGGL(dec_classify_kernel<true>, grid, block, 0, stream, p, (const uint4*)raw, evs, nev32, prow, nd32,
                          a->maxd, blockp, blk, changes, 1);
-      if (hipMemcpyAsync(a->h_scratch + 8, blk, 8, hipMemcpyDeviceToHost, stream) != hipSuccess) return -5;
+      if (hipMemcpyAsync(a->h_scratch + 8, blk, 8, hipMemcpyDeviceToHost, stream) != hipSuccess) return XCG_RC_HIP;
       int same = 0;
       const PairGpu G = pair_gpu(a, prow);
       const int prc = xcg_pair_decode_pass(a->pair, &G, evs, p.decl_base, p.n_decl, n, ndecl, a->maxd, &same, stream);
@@ -1758,12 +1758,12 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
       agreed = same && nb == blockp;
       blockp = nb;
     }
-    if (!agreed) return -75;
+    if (!agreed) return XCG_RC_OVERFLOW;
   }
   uint4* dfull = nullptr;
   if (nbref > 0 && ndecl > 0) {
     // BACKREFs present: records of every declare (rare; never made by XCodecEncoder)
-    if (!dfull_tmp.alloc(&dfull, 16ull * ndecl)) return -5;
+    if (!dfull_tmp.alloc(&dfull, 16ull * ndecl)) return XCG_RC_HIP;
     p.D = dfull;
     p.D_lo = 0;
     p.D_tail = false;
@@ -1783,7 +1783,7 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
       hipMemcpyAsync(a->h_scratch + 6, a->nunknown, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
       hipMemcpyAsync(a->h_scratch + 10, a->status, 4, hipMemcpyDeviceToHost, stream) != hipSuccess ||
       hipStreamSynchronize(stream) != hipSuccess)
-    return -5;
+    return XCG_RC_HIP;
   const uint32_t nconf = (uint32_t)(a->h_scratch[6] >> 32);
   a->h_scratch[13] = nconf;
   if (a->h_scratch[10] & (1u << 9)) {
@@ -1791,13 +1791,13 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
     a->h_scratch[11] = a->h_scratch[10] & ~(uint64_t)(1u << 9);
     (void)hipMemcpyAsync(a->status, a->h_scratch + 11, 4, hipMemcpyHostToDevice, stream);
     (void)hipStreamSynchronize(stream);
-    return -95;
+    return XCG_RC_NOTSUP;
   }
   *total_out = a->h_scratch[0];
   *block_pos_out = a->h_scratch[1];
   *berr_pos_out = a->h_scratch[2];
   *nunknown_out = (uint32_t)(a->h_scratch[6] & 0xFFFFFFFFu);
-  if (*total_out > a->out_cap) return -75;
+  if (*total_out > a->out_cap) return XCG_RC_OVERFLOW;
   // Name reuse (hashes whose EXTRACTs differ; unbounded contexts only get
   // here): their occurrences sorted by (hash, position) -- a stable sort by
   // position, then by hash -- for the REUSE kernels' binary search.
@@ -1809,18 +1809,18 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
     if (rocprim::radix_sort_pairs(nullptr, tmp1, v0, v1, k0, k1, m, 0, 64, stream) != hipSuccess ||
         rocprim::radix_sort_pairs(nullptr, tmp2, k1, k0, v1, v0, m, 0, 64, stream) != hipSuccess ||
         !occ_tmp.alloc(&occ_mem, 32ull * m + 256 + (tmp1 > tmp2 ? tmp1 : tmp2)))
-      return -5;
+      return XCG_RC_HIP;
     k0 = (uint64_t*)occ_mem; k1 = k0 + m; v0 = k1 + m; v1 = v0 + m;
     void* tmp = (void*)(((uintptr_t)(v1 + m) + 255) & ~(uintptr_t)255);
     uint32_t* nocc = a->nunknown + 2;
-    if (hipMemsetAsync(occ_mem, 0xFF, 32ull * m, stream) != hipSuccess) return -5;
+    if (hipMemsetAsync(occ_mem, 0xFF, 32ull * m, stream) != hipSuccess) return XCG_RC_HIP;
     hipLaunchKernelGGL(dec_occ_owner_kernel, dim3((unsigned)(((uint64_t)a->x_mask + 256) / 256)), dim3(256), 0, stream,
                        p, k0, v0, nocc, m);
     hipLaunchKernelGGL(dec_occ_dup_kernel, dim3((unsigned)((ndup + 255) / 256)), dim3(256), 0, stream, p, (uint32_t)ndup,
                        k0, v0, nocc, m);
     if (rocprim::radix_sort_pairs(tmp, tmp1, v0, v1, k0, k1, m, 0, 64, stream) != hipSuccess ||
         rocprim::radix_sort_pairs(tmp, tmp2, k1, k0, v1, v0, m, 0, 64, stream) != hipSuccess)
-      return -5;
+      return XCG_RC_HIP;
     p.occ_key = k0;
     p.occ_pos = v0;
     p.nocc = m;
@@ -1859,7 +1859,7 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
     const PairGpu G = pair_gpu(a, prow);
     const int crc = xcg_pair_decode_commit(a->pair, &G, stream);
     if (crc) return crc;
-    return hipGetLastError() == hipSuccess ? 0 : -5;
+    return hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
   }
   if (a->lru) {
     hipLaunchKernelGGL(dec_replace_kernel, grid, block, 0, stream, p, (const uint4*)raw, (const uint4*)evs, a->g.pool);
@@ -1876,7 +1876,7 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
                          a->g.pool, a->g.nseg, a->g.seg_cap, fs);
     seg3.end();
   }
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
 }
 
 // One decode() call on an unbounded cache in one launch (decode_small_kernel).
@@ -1908,7 +1908,7 @@ extern "C" int xcg_launch_decode_small(const uint8_t* in, uint32_t len, const Xc
   a.flag = flag;
   a.seq = seq;
   hipLaunchKernelGGL(decode_small_kernel, dim3(1), dim3(1024), 0, stream, a);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
 }
 
 extern "C" uint64_t xcg_decode_small_scratch(uint32_t ops_cap) { return 40ull * ops_cap; }

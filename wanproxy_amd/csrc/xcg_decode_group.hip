@@ -185,7 +185,7 @@ extern "C" int xcg_launch_decode_group(const XcgGroupDecodeArgs* a, hipStream_t 
   } else if (a->max_len <= XCG_GROUP_DEC_LARGE) {
     hipLaunchKernelGGL((xcg::decode_group_kernel<1024>), grid, block, 0, stream, *a);
   } else {
-    return -22;
+    return XCG_RC_INVAL;
   }
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
 }

@@ -152,7 +152,7 @@ extern "C" int xcg_launch_decode_independent(const XcgIndepDecodeArgs* a, hipStr
   } else if (a->max_len <= XCG_INDEP_DEC_LARGE) {
     hipLaunchKernelGGL((xcg::decode_independent_kernel<1024>), grid, block, 0, stream, *a);
   } else {
-    return -22;
+    return XCG_RC_INVAL;
   }
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
 }

@@ -88,7 +88,7 @@ extern "C" int xcg_launch_encode_group(const uint8_t* d_in, const uint64_t* d_ch
   } else if (max_group_len <= (1u << 19)) {
     hipLaunchKernelGGL((encode_group_kernel<11, 264>), grid, block, 0, stream, prm, d_group_first, n_groups);
   } else {
-    return -22;
+    return XCG_RC_INVAL;
   }
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
 }

@@ -35,7 +35,7 @@ extern "C" int xcg_launch_encode_independent(const uint8_t* d_in, const uint64_t
   } else if (max_chunk_len <= (1u << 19)) {
     hipLaunchKernelGGL((encode_independent_kernel<11, 264>), grid, block, 0, stream, prm);
   } else {
-    return -22;
+    return XCG_RC_INVAL;
   }
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
 }

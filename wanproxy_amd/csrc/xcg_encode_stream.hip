@@ -731,7 +731,7 @@ extern "C" int xcg_launch_seed_tiling(const XcgStreamArgs* a, hipStream_t stream
   hipLaunchKernelGGL(xcg::seed_tiling_kernel, dim3((seed_waves + 3) / 4), dim3(256), 0, stream, a->in, a->chunk_off,
                      a->chunk_len, a->n, a->maxd, (uint4*)a->decl, a->ndecl, a->nhits, a->changed,
                      xcg::HashTab{nullptr, nullptr, 0u}, xcg::FiltSet{}, nullptr, nullptr, 0u);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
 }
 
 // Live timing of the stream-parse kernel for bench.py's roofline: while on,
@@ -755,7 +755,7 @@ extern "C" int xcg_debug_stream_kernel_time(double* ms, uint32_t* launches) {
   for (auto& e : g_ktime_ev) {
     float t = 0;
     if (hipEventSynchronize(e.second) != hipSuccess || hipEventElapsedTime(&t, e.first, e.second) != hipSuccess)
-      rc = -5;
+      rc = XCG_RC_HIP;
     tot += t;
     (void)hipEventDestroy(e.first);
     (void)hipEventDestroy(e.second);
@@ -833,7 +833,7 @@ extern "C" int xcg_launch_encode_stream(const XcgStreamArgs* a, int* rounds_out,
   int cus = 0;
   if (hipGetDevice(&dev) != hipSuccess ||
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return -5;
+    return XCG_RC_HIP;
   const uint32_t wgs = (uint32_t)cus;
   const bool big = a->maxd > 72;                     // chunks > 128 KiB (<= 512 KiB frames): 264 records
   // One workgroup per CU (LDS): SW chunk-waves each.  A batch too small to
@@ -896,7 +896,7 @@ extern "C" int xcg_launch_encode_stream(const XcgStreamArgs* a, int* rounds_out,
   if (!seeded && (hipMemsetAsync(a->ndecl, 0, 4ull * n, stream) != hipSuccess ||
                   hipMemsetAsync(a->nhits, 0, 4ull * n, stream) != hipSuccess ||
                   hipMemsetAsync(a->changed, 0xFF, 4, stream) != hipSuccess))
-    return -5;                                       // (the seed kernel initialises these itself)
+    return XCG_RC_HIP;                                       // (the seed kernel initialises these itself)
   if (a->decls_out) *a->decls_out = ~0u;
   prm.need = nullptr;
   prm.hits = a->hits;                              // every stream round writes nhits[chunk]
@@ -939,7 +939,7 @@ extern "C" int xcg_launch_encode_stream(const XcgStreamArgs* a, int* rounds_out,
     // sit on their inserts at low occupancy (C4's 4 KiB packets: seed 66 ->
     // 342 us), so the separate build keeps them.
     const bool fuse = a->maxd > SEED_TILES;
-    if (fuse && !prep(cur, false, PREP_TABLE | PREP_FILTERS)) return -5;
+    if (fuse && !prep(cur, false, PREP_TABLE | PREP_FILTERS)) return XCG_RC_HIP;
     const uint32_t seed_waves = n * ((a->maxd + SEED_TILES - 1) / SEED_TILES);
     hipLaunchKernelGGL(seed_tiling_kernel, dim3((seed_waves + 3) / 4), dim3(256), 0, stream, a->in, a->chunk_off,
                        a->chunk_len, n, a->maxd, (uint4*)a->decl, a->ndecl, a->nhits, a->changed,
@@ -951,7 +951,7 @@ extern "C" int xcg_launch_encode_stream(const XcgStreamArgs* a, int* rounds_out,
     launch();
     rounds = 1;
     // (one chunk: no round follows, so no need to learn what it declared)
-    if (n > 1 && !changed_after(fc)) return -5;
+    if (n > 1 && !changed_after(fc)) return XCG_RC_HIP;
     if (n > 1 && fc == ~0u && a->decls_out) *a->decls_out = 0;   // round 0 declared nothing
   }
   // Jacobi rounds: chunk k re-parses against the declarations chunks < k made
@@ -1013,7 +1013,7 @@ extern "C" int xcg_launch_encode_stream(const XcgStreamArgs* a, int* rounds_out,
     }
   };
   if (n > 1 && fc != ~0u) {
-    if (!seed_built && !build(cur, false, PREP_TABLE | PREP_FILTERS)) return -5;
+    if (!seed_built && !build(cur, false, PREP_TABLE | PREP_FILTERS)) return XCG_RC_HIP;
     prm.use_b = true;
     prm.b = tabs[cur];
     prm.skip_below = seeded ? 0 : fc + 1;            // (seeded: round 1 parses every chunk)
@@ -1032,7 +1032,7 @@ extern "C" int xcg_launch_encode_stream(const XcgStreamArgs* a, int* rounds_out,
     for (uint32_t r = 2; r <= n + 1; ++r) {
       // verify round r-1 (parsed against tabs[cur]) against its own declarations
       const int nxt = cur ^ 1;
-      if (!build(nxt, true, PREP_TABLE)) return -5;   // (filters only if a re-parse follows)
+      if (!build(nxt, true, PREP_TABLE)) return XCG_RC_HIP;   // (filters only if a re-parse follows)
       const uint64_t slots = 2ull * (a->b_mask + 1);
       hipLaunchKernelGGL(verify_diff_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, stream, tabs[cur],
                          tabs[nxt], a->in, a->chunk_off, rt, a->vflags, at, a->a_bits, a->status);
@@ -1055,15 +1055,15 @@ extern "C" int xcg_launch_encode_stream(const XcgStreamArgs* a, int* rounds_out,
         v.at = at; v.abits = (const uint32_t*)a->a_bits; v.rt = rt; v.bcount = (const uint32_t*)a->bcount;
         hipLaunchKernelGGL(verify_flags_kernel, dim3(v.bc + v.bp + v.bh), dim3(256), 0, stream, v);
       }
-      if (hipMemcpyAsync(a->h_vflags, a->vflags, 16, hipMemcpyDeviceToHost, stream) != hipSuccess) return -5;
+      if (hipMemcpyAsync(a->h_vflags, a->vflags, 16, hipMemcpyDeviceToHost, stream) != hipSuccess) return XCG_RC_HIP;
       // The host waits for the flags alone: the commit (a no-op if anything was
       // flagged) runs on the device while the host returns and queues the next
       // batch behind it, so the device does not idle through the host's turn.
       const hipEvent_t vev = flags_ev.ev;
-      if (!vev || hipEventRecord(vev, stream) != hipSuccess) return -5;
+      if (!vev || hipEventRecord(vev, stream) != hipSuccess) return XCG_RC_HIP;
       commit(a->vflags + 1);
-      if (a->post_verify && a->post_verify(a->post_user, a->vflags + 1, stream)) return -5;
-      if (hipEventSynchronize(vev) != hipSuccess) return -5;
+      if (a->post_verify && a->post_verify(a->post_user, a->vflags + 1, stream)) return XCG_RC_HIP;
+      if (hipEventSynchronize(vev) != hipSuccess) return XCG_RC_HIP;
       if (a->decls_out) *a->decls_out = a->h_vflags[2];
       if (stream_debug())
         fprintf(stderr, "stream: n %u round %u first (a)-flag %d any %u newly visible %u\n", n, r,
@@ -1073,8 +1073,8 @@ extern "C" int xcg_launch_encode_stream(const XcgStreamArgs* a, int* rounds_out,
         committed = true;
         break;
       }
-      if (hipMemsetAsync(a->changed, 0xFF, 4, stream) != hipSuccess) return -5;
-      if (!build(nxt, false, PREP_FILTERS)) return -5;   // the re-parse's filters: cache + round r-1's lists
+      if (hipMemsetAsync(a->changed, 0xFF, 4, stream) != hipSuccess) return XCG_RC_HIP;
+      if (!build(nxt, false, PREP_FILTERS)) return XCG_RC_HIP;   // the re-parse's filters: cache + round r-1's lists
       cur = nxt;
       prm.b = tabs[cur];
       prm.need = a->need;
@@ -1082,7 +1082,7 @@ extern "C" int xcg_launch_encode_stream(const XcgStreamArgs* a, int* rounds_out,
       else launch();                                 // (flagged by the verification: from the start)
       ++rounds;
     }
-    if (!converged) return -75;
+    if (!converged) return XCG_RC_OVERFLOW;
   }
   // A result no verification passed over (one chunk, or round 0 declared
   // nothing): an own-table overflow in it is reported (status bit 0).
@@ -1090,5 +1090,5 @@ extern "C" int xcg_launch_encode_stream(const XcgStreamArgs* a, int* rounds_out,
                                      (const uint32_t*)a->nhits, n, a->maxh, a->status);
   if (!committed) commit(nullptr);
   if (rounds_out) *rounds_out = rounds;
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
 }

@@ -89,7 +89,7 @@ extern "C" int xcg_launch_window_hashes(const uint8_t* d_x, uint64_t len, uint64
   const uint64_t waves = (npos + xcg::SEG - 1) / xcg::SEG;
   hipLaunchKernelGGL(xcg::window_hashes_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, d_x,
                      (int64_t)len, d_hash);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
 }
 
 extern "C" int xcg_launch_segment_hashes(const uint8_t* d_x, uint64_t len, uint64_t* d_hash, hipStream_t stream) {
@@ -97,5 +97,5 @@ extern "C" int xcg_launch_segment_hashes(const uint8_t* d_x, uint64_t len, uint6
   if (nseg == 0) return 0;
   hipLaunchKernelGGL(xcg::segment_hashes_kernel, dim3((unsigned)((nseg + 255) / 256)), dim3(256), 0, stream, d_x,
                      (int64_t)nseg, d_hash);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
 }

@@ -525,11 +525,11 @@ using xcg::grid_for;
 template <int K>
 int run_scan(XcgLruState* L, xcg::ScanArgs a, uint64_t max_n, hipStream_t st) {
   const uint32_t tiles = (uint32_t)((max_n + 1023) / 1024) + 1;
-  if (!L->mem->grow(&L->part, &L->part_cap, tiles, tiles * 2, 4ull * tiles * 2, xcg::MEM_DEV)) return -5;
+  if (!L->mem->grow(&L->part, &L->part_cap, tiles, tiles * 2, 4ull * tiles * 2, xcg::MEM_DEV)) return XCG_RC_HIP;
   a.part = L->part;
   hipLaunchKernelGGL(xcg::scan_count_kernel<K>, dim3(tiles), dim3(256), 0, st, a);
   hipLaunchKernelGGL(xcg::scan_emit_kernel<K>, dim3(tiles), dim3(256), 0, st, a);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
 }
 
 xcg::ScanArgs scan_args(XcgLruState* L, const LruBatch& b, uint32_t* nseg) {
@@ -585,21 +585,22 @@ int lru_times(const LruBatch& b, XcgLruState* L, bool check, hipStream_t st, boo
                      (const uint32_t*)L->tot, L->C, L->hmin, L->tau, skip);
   ScanArgs ra = scan_args(L, b, nullptr);
   ra.gate = skip;
-  if (run_scan<SK_RANK>(L, ra, L->C, st)) return -5;
+  if (run_scan<SK_RANK>(L, ra, L->C, st)) return XCG_RC_HIP;
   if (check)
     hipLaunchKernelGGL(lru_check_kernel, wgrid, dim3(256), 0, st, n, R, (const uint64_t*)L->hmin,
                        (const uint64_t*)L->wpop, b.need, L->tot, b.bad_t, b.bad_hi, skip);
   if (!sync) {                                     // (the caller waits on L->tev after queueing more)
     hipLaunchKernelGGL(lru_gate_kernel, dim3(1), dim3(64), 0, st, L->tot, L->C, skip);
-    if (!L->tev && hipEventCreateWithFlags((hipEvent_t*)&L->tev, hipEventDisableTiming) != hipSuccess) return -5;
+    if (!L->tev && hipEventCreateWithFlags((hipEvent_t*)&L->tev, hipEventDisableTiming) != hipSuccess)
+      return XCG_RC_HIP;
     if (hipMemcpyAsync(L->h_tot, L->tot, 4 * T_WORDS, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipEventRecord((hipEvent_t)L->tev, st) != hipSuccess)
-      return -5;
+      return XCG_RC_HIP;
     return 0;
   }
   if (hipMemcpyAsync(L->h_tot, L->tot, 4 * T_WORDS, hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipStreamSynchronize(st) != hipSuccess)
-    return -5;
+    return XCG_RC_HIP;
   return 0;
 }
 
@@ -645,7 +646,7 @@ int lru_seed_guess(const XcgStreamArgs& a, XcgLruState* L, hipStream_t st) {
                        (const uint32_t*)L->tot, L->C, L->hmin, L->tau, 1, pt);
     ScanArgs sa = scan_args(L, lb, nullptr);
     if (it + 1 < iters) sa.hmin_reset = L->hmin;
-    if (run_scan<SK_RANK>(L, sa, L->C, st)) return -5;
+    if (run_scan<SK_RANK>(L, sa, L->C, st)) return XCG_RC_HIP;
   }
   return 0;
 }
@@ -668,7 +669,7 @@ int lru_commit_dev(const LruBatch* bp, XcgLruState* L, const uint32_t* gate, hip
                      (const uint32_t*)L->queue, (const uint64_t*)L->hmin, (const uint64_t*)L->wpop, L->alive, gate);
   ScanArgs fa = scan_args(L, b, nullptr);
   fa.gate = gate;
-  if (run_scan<SK_FREE>(L, fa, C, st)) return -5;
+  if (run_scan<SK_FREE>(L, fa, C, st)) return XCG_RC_HIP;
   const HashTab g = tab_of(b.g);
   const FiltSet fs = filters_of(b.g);
   Wipe w{g, fs.filt, (u32x4*)fs.ftab, fs.fmask + 1, fs.gfilt, fs.gmask + 1};
@@ -685,9 +686,9 @@ int lru_commit_dev(const LruBatch* bp, XcgLruState* L, const uint32_t* gate, hip
   {
     ScanArgs qa = scan_args(L, b, b.g.nseg);
     qa.gate = gate;
-    if (run_scan<SK_QUEUE>(L, qa, (uint64_t)C + b.ev_bound, st)) return -5;
+    if (run_scan<SK_QUEUE>(L, qa, (uint64_t)C + b.ev_bound, st)) return XCG_RC_HIP;
   }
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
 }
 
 // The host side of a commit that happened: the new LRU order, the clock.
@@ -700,7 +701,7 @@ void lru_commit_host(XcgLruState* L, uint32_t n) {
 }  // namespace
 
 extern "C" int xcg_lru_commit(const LruBatch* bp, XcgLruState* L, hipStream_t st) {
-  if (lru_commit_dev(bp, L, nullptr, st)) return -5;
+  if (lru_commit_dev(bp, L, nullptr, st)) return XCG_RC_HIP;
   lru_commit_host(L, bp->n);
   return 0;
 }
@@ -720,22 +721,22 @@ extern "C" int xcg_lru_rebuild_table(const XcgCacheView* gv, XcgLruState* L, int
   hipLaunchKernelGGL(lru_wipe_kernel, dim3(1024), dim3(256), 0, st, w, (const uint32_t*)nullptr);
   hipLaunchKernelGGL(lru_insert_alive_kernel, dim3(grid_for(L->C)), dim3(256), 0, st, L->C, (const uint32_t*)L->alive,
                      (const uint64_t*)L->skey, g, fs, status, (const uint32_t*)nullptr);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
 }
 
 extern "C" int xcg_lru_reset_times(XcgLruState* L, hipStream_t st) {
   using namespace xcg;
   const unsigned cg = grid_for(L->C) < 1024 ? grid_for(L->C) : 1024;
   hipLaunchKernelGGL(lru_fill64_kernel, dim3(cg), dim3(256), 0, st, L->ptime, L->C, NEVER);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
 }
 
 // Stream-semantics encode of a batch on a bounded cache.  The batch is cut
 // into sub-batches with N + H <= C (the bound the eviction rule above needs; a
 // sub-batch that exceeds it is halved); each is parsed
 // (xcg_launch_encode_stream, commit off) until its eviction times are
-// consistent, then committed.  Returns 0, -75 (no fixed point / reference
-// list overflow), -95 (one chunk alone exceeds the bound), -5.
+// consistent, then committed.  Returns 0, XCG_RC_OVERFLOW (no fixed point / reference
+// list overflow), XCG_RC_NOTSUP (one chunk alone exceeds the bound), XCG_RC_HIP.
 extern "C" int xcg_lru_encode_stream(const XcgStreamArgs* a0, XcgLruState* L, int* rounds_out, hipStream_t st) {
   using namespace xcg;
   const uint32_t n = a0->n, C = L->C;
@@ -775,7 +776,7 @@ extern "C" int xcg_lru_encode_stream(const XcgStreamArgs* a0, XcgLruState* L, in
       Hook* h = (Hook*)u;
       const LruBatch b = batch_of(*h->a);
       h->fired = true;
-      if (lru_times(b, h->L, true, s, false, vbusy)) return -5;
+      if (lru_times(b, h->L, true, s, false, vbusy)) return XCG_RC_HIP;
       return lru_commit_dev(&b, h->L, h->L->tot + T_GATE, s);
     };
     using clk = std::chrono::steady_clock;
@@ -783,8 +784,8 @@ extern "C" int xcg_lru_encode_stream(const XcgStreamArgs* a0, XcgLruState* L, in
     auto dsync = [&]() { if (lru_debug()) (void)hipStreamSynchronize(st); return clk::now(); };
     const clk::time_point t0 = dsync();
     // Pass 0 starts from the tiling seed, with the evictions it implies.
-    if (xcg_launch_seed_tiling(&a, st)) return -5;
-    if (lru_seed_guess(a, L, st)) return -5;
+    if (xcg_launch_seed_tiling(&a, st)) return XCG_RC_HIP;
+    if (lru_seed_guess(a, L, st)) return XCG_RC_HIP;
     const clk::time_point t1 = dsync();
     bool done = false, split = false;
     for (int pass = 0; pass < MAX_PASSES && !done && !split; ++pass) {
@@ -802,10 +803,10 @@ extern "C" int xcg_lru_encode_stream(const XcgStreamArgs* a0, XcgLruState* L, in
       // time the host waits for them.
       if (!hook.fired) {                             // (no verification ran: one chunk, or nothing declared)
         const LruBatch b = batch_of(a);
-        if (lru_times(b, L, true, st, false)) return -5;
-        if (lru_commit_dev(&b, L, L->tot + T_GATE, st)) return -5;
+        if (lru_times(b, L, true, st, false)) return XCG_RC_HIP;
+        if (lru_commit_dev(&b, L, L->tot + T_GATE, st)) return XCG_RC_HIP;
       }
-      if (hipEventSynchronize((hipEvent_t)L->tev) != hipSuccess) return -5;
+      if (hipEventSynchronize((hipEvent_t)L->tev) != hipSuccess) return XCG_RC_HIP;
       const clk::time_point q2 = dsync();
       if (lru_debug()) {
         int32_t stw = 0;
@@ -815,12 +816,12 @@ extern "C" int xcg_lru_encode_stream(const XcgStreamArgs* a0, XcgLruState* L, in
                 i0, m, pass, r, L->h_tot[T_E], L->h_tot[T_N], L->h_tot[T_P], L->h_tot[T_A], L->h_tot[T_BAD],
                 L->h_tot[T_OVF], stw, pass == 0 ? ms(t0, t1) : 0.0, ms(q0, q1), ms(q1, q2));
       }
-      if (L->h_tot[T_OVF]) return -75;
+      if (L->h_tot[T_OVF]) return XCG_RC_OVERFLOW;
       if ((uint64_t)L->h_tot[T_N] + L->h_tot[T_H] > C) split = true;
       else if (L->h_tot[T_BAD] == 0) done = true;
     }
     if (!done) {
-      if (m == 1) return split ? -95 : -75;
+      if (m == 1) return split ? XCG_RC_NOTSUP : XCG_RC_OVERFLOW;
       per = m / 2;                                   // redo this part in halves
       continue;
     }
@@ -849,5 +850,5 @@ extern "C" int xcg_lru_encode_stream(const XcgStreamArgs* a0, XcgLruState* L, in
     per = (uint32_t)(want < 1 ? 1 : (want > n ? n : want));
   }
   if (rounds_out) *rounds_out = rounds;
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
 }

@@ -275,7 +275,7 @@ __global__ __launch_bounds__(256) void pr_resolve_kernel(PairDev d) {
       }
     }
   }
-  if (kk != K_SKIP && d.ent[pos] >= d.etot) {        // (a decode HIT with no definer: the pass returns -95)
+  if (kk != K_SKIP && d.ent[pos] >= d.etot) {        // (a decode HIT with no definer: the pass returns XCG_RC_NOTSUP)
     kk = K_SKIP;
     d.kind[pos] = kk;
   }
@@ -1047,7 +1047,7 @@ int ensure_scratch(XcgPairState* P, uint64_t np, uint64_t n, uint64_t etot) {
     for (const Arr& a : arrs) m.release(*a.p), *a.p = nullptr;
     P->np_cap = 0;
     for (const Arr& a : arrs)
-      if (!m.dev(a.p, (cap + 1) * a.sz)) return -5;
+      if (!m.dev(a.p, (cap + 1) * a.sz)) return XCG_RC_HIP;
     P->np_cap = cap;
   }
   if (n + 1 > P->n_cap) {
@@ -1055,16 +1055,16 @@ int ensure_scratch(XcgPairState* P, uint64_t np, uint64_t n, uint64_t etot) {
     m.release(P->pcnt);
     P->pbase = P->pcnt = nullptr;
     P->n_cap = 0;
-    if (!(m.dev(&P->pbase, 4 * (n + 1)) && m.dev(&P->pcnt, 4 * (n + 1)))) return -5;
+    if (!(m.dev(&P->pbase, 4 * (n + 1)) && m.dev(&P->pcnt, 4 * (n + 1)))) return XCG_RC_HIP;
     P->n_cap = n + 1;
   }
-  if (!m.grow_exact(&P->erun, &P->et_cap, etot) || !m.grow_exact(&P->elast, &P->el_cap, etot)) return -5;
+  if (!m.grow_exact(&P->erun, &P->et_cap, etot) || !m.grow_exact(&P->elast, &P->el_cap, etot)) return XCG_RC_HIP;
   if (etot > P->ex_cap) {
     const Arr arrs[] = {ARR(erend), ARR(einit), ARR(ecov), ARR(egap), ARR(etail)};
     P->ex_cap = 0;
     for (const Arr& a : arrs) m.release(*a.p), *a.p = nullptr;
     for (const Arr& a : arrs)
-      if (!m.dev(a.p, etot * a.sz + 8)) return -5;
+      if (!m.dev(a.p, etot * a.sz + 8)) return XCG_RC_HIP;
     P->ex_cap = etot;
   }
 #undef ARR
@@ -1081,41 +1081,41 @@ int ensure_scratch(XcgPairState* P, uint64_t np, uint64_t n, uint64_t etot) {
   (void)rocprim::inclusive_scan(nullptr, e2, P->sa, P->sb, (size_t)np + 1, rocprim::maximum<uint64_t>());
   (void)rocprim::inclusive_scan(nullptr, e3, P->sa, P->sb, (size_t)np + 1, rocprim::minimum<uint64_t>());
   const uint64_t want = std::max(std::max(std::max(a, b), c), std::max(std::max(e1, e2), e3)) + 256;
-  return m.grow(&P->tmp, &P->tmp_cap, want, want, want, MEM_DEV) ? 0 : -5;
+  return m.grow(&P->tmp, &P->tmp_cap, want, want, want, MEM_DEV) ? 0 : XCG_RC_HIP;
 }
 
 int scan_u32(XcgPairState* P, const uint32_t* in, uint32_t* out, uint64_t n, hipStream_t st) {
   size_t tb = P->tmp_cap;
   return rocprim::exclusive_scan(P->tmp, tb, in, out, 0u, (size_t)n, rocprim::plus<uint32_t>(), st) == hipSuccess
-             ? 0 : -5;
+             ? 0 : XCG_RC_HIP;
 }
 
 // Segmented max / min scans of the packed (run << 32 | v) values (sa -> sb).
 int scan_max_excl(XcgPairState* P, uint64_t n, hipStream_t st) {
   size_t tb = P->tmp_cap;
   return rocprim::exclusive_scan(P->tmp, tb, P->sa, P->sb, (uint64_t)0, (size_t)n, rocprim::maximum<uint64_t>(),
-                                 st) == hipSuccess ? 0 : -5;
+                                 st) == hipSuccess ? 0 : XCG_RC_HIP;
 }
 int scan_max_incl(XcgPairState* P, uint64_t n, hipStream_t st) {
   size_t tb = P->tmp_cap;
   return rocprim::inclusive_scan(P->tmp, tb, P->sa, P->sb, (size_t)n, rocprim::maximum<uint64_t>(), st) == hipSuccess
-             ? 0 : -5;
+             ? 0 : XCG_RC_HIP;
 }
 int scan_min_incl(XcgPairState* P, uint64_t n, hipStream_t st) {
   size_t tb = P->tmp_cap;
   return rocprim::inclusive_scan(P->tmp, tb, P->sa, P->sb, (size_t)n, rocprim::minimum<uint64_t>(), st) == hipSuccess
-             ? 0 : -5;
+             ? 0 : XCG_RC_HIP;
 }
 
 int read_small(XcgPairState* P, const void* src, size_t bytes, hipStream_t st) {
   return hipMemcpyAsync(P->h_small, src, bytes, hipMemcpyDeviceToHost, st) == hipSuccess &&
                  hipStreamSynchronize(st) == hipSuccess
-             ? 0 : -5;
+             ? 0 : XCG_RC_HIP;
 }
 int read_cnt(XcgPairState* P, hipStream_t st) {
   return hipMemcpyAsync(P->h_cnt, P->cnt, sizeof(PairCnt), hipMemcpyDeviceToHost, st) == hipSuccess &&
                  hipStreamSynchronize(st) == hipSuccess
-             ? 0 : -5;
+             ? 0 : XCG_RC_HIP;
 }
 
 // Where the rows of a pass come from.
@@ -1147,14 +1147,14 @@ int replay(XcgPairState* P, const RowSrc& rs, const HashTab& g, bool want_leave,
   const uint32_t n = rs.n;
   const uint32_t newb = P->C + P->D;
   const uint64_t etot64 = (uint64_t)newb + (uint64_t)n * rs.maxd;
-  if (etot64 >= (1ull << 31)) return -95;
+  if (etot64 >= (1ull << 31)) return XCG_RC_NOTSUP;
   const uint32_t etot = (uint32_t)etot64;
   if (!P->cnt) {
     if (!(P->mem.dev(&P->cnt, sizeof(PairCnt)) && P->mem.pinned(&P->h_cnt, sizeof(PairCnt)) &&
           P->mem.pinned(&P->h_small, 256)))
-      return -5;
+      return XCG_RC_HIP;
   }
-  if (hipMemsetAsync(P->cnt, 0, sizeof(PairCnt), st) != hipSuccess) return -5;
+  if (hipMemsetAsync(P->cnt, 0, sizeof(PairCnt), st) != hipSuccess) return XCG_RC_HIP;
   PairDev d{};
   d.C = P->C; d.xuid = P->xuid; d.P = P->pcount;
   d.pkey = P->pkey; d.pdisk = P->pdisk; d.lru = P->lru; d.ptime = P->ptime;
@@ -1167,20 +1167,20 @@ int replay(XcgPairState* P, const RowSrc& rs, const HashTab& g, bool want_leave,
   d.g = g;
   // rows per chunk -> positions
   uint64_t R;
-  if (ensure_scratch(P, (uint64_t)P->pcount + 1, n, etot)) return -5;
+  if (ensure_scratch(P, (uint64_t)P->pcount + 1, n, etot)) return XCG_RC_HIP;
   if (!rs.dec) {
     d.pbase = P->pbase;
     d.pcnt = P->pcnt;
     d.cnt = P->cnt;
     hipLaunchKernelGGL(pr_count_kernel, dim3(grid_for(n + 1)), dim3(256), 0, st, d);
-    if (scan_u32(P, P->pcnt, P->pbase, (uint64_t)n + 1, st) || read_small(P, P->pbase + n, 4, st)) return -5;
+    if (scan_u32(P, P->pcnt, P->pbase, (uint64_t)n + 1, st) || read_small(P, P->pbase + n, 4, st)) return XCG_RC_HIP;
     R = P->h_small[0];
   } else {
     R = rs.rows;
   }
   const uint64_t np = (uint64_t)P->pcount + R;
-  if (np >= (1ull << 31)) return -95;
-  if (ensure_scratch(P, np, n, etot)) return -5;
+  if (np >= (1ull << 31)) return XCG_RC_NOTSUP;
+  if (ensure_scratch(P, np, n, etot)) return XCG_RC_HIP;
   d.np = (uint32_t)np;
   d.ent = P->ent; d.yent = P->yent; d.kind = P->kind; d.tim = P->tim; d.hsh = P->hsh;
   d.skey = P->skey; d.sval = P->sval; d.sk = P->sk; d.sv = P->sv; d.prv = P->prv; d.nxt = P->nxt;
@@ -1194,13 +1194,13 @@ int replay(XcgPairState* P, const RowSrc& rs, const HashTab& g, bool want_leave,
   if (!rs.dec) {
     const uint64_t want = std::max<uint64_t>(1024, 2ull << (64 - __builtin_clzll(R + 1)));
     uint64_t kc = P->bm_cap, vc = P->bm_cap;
-    if (!P->mem.grow_exact(&P->bm_keys, &kc, want) || !P->mem.grow_exact(&P->bm_vals, &vc, want)) return -5;
+    if (!P->mem.grow_exact(&P->bm_keys, &kc, want) || !P->mem.grow_exact(&P->bm_vals, &vc, want)) return XCG_RC_HIP;
     P->bm_cap = std::min(kc, vc);
     d.bm = HashTab{P->bm_keys, P->bm_vals, (uint32_t)(want - 1)};
     hipLaunchKernelGGL(pr_fill64_kernel, dim3(grid_for(want)), dim3(256), 0, st, P->bm_keys, want, EMPTY_KEY);
     hipLaunchKernelGGL(pr_fill64_kernel, dim3(grid_for(want)), dim3(256), 0, st, P->bm_vals, want, ~0ull);
   }
-  if (hipMemsetAsync(P->tflag, 0, np + 1, st) != hipSuccess) return -5;
+  if (hipMemsetAsync(P->tflag, 0, np + 1, st) != hipSuccess) return XCG_RC_HIP;
   if (rs.dec) hipLaunchKernelGGL(pr_fill32_kernel, dim3(grid_for(newb)), dim3(256), 0, st, P->erep, (uint64_t)newb, NIL);
   hipLaunchKernelGGL(pr_fill32_kernel, dim3(grid_for(etot)), dim3(256), 0, st, P->erun, (uint64_t)etot, NIL);
   if (P->pcount) hipLaunchKernelGGL(pr_pseudo_kernel, dim3(grid_for(P->pcount)), dim3(256), 0, st, d);
@@ -1209,22 +1209,22 @@ int replay(XcgPairState* P, const RowSrc& rs, const HashTab& g, bool want_leave,
     uint64_t c1 = P->hk_cap, c2 = P->hk_cap, c3 = P->hk_cap, c4 = P->hk_cap;
     if (!P->mem.grow_exact(&P->hk, &c1, R) || !P->mem.grow_exact(&P->hk2, &c2, R) ||
         !P->mem.grow_exact(&P->hv, &c3, R) || !P->mem.grow_exact(&P->hv2, &c4, R))
-      return -5;
+      return XCG_RC_HIP;
     P->hk_cap = std::min(std::min(c1, c2), std::min(c3, c4));
-    if (hipMemcpyAsync(P->hk, P->hsh + P->pcount, 8 * R, hipMemcpyDeviceToDevice, st) != hipSuccess) return -5;
+    if (hipMemcpyAsync(P->hk, P->hsh + P->pcount, 8 * R, hipMemcpyDeviceToDevice, st) != hipSuccess) return XCG_RC_HIP;
     // values: positions P .. np-1
     hipLaunchKernelGGL(pr_iota_kernel, dim3(grid_for(R)), dim3(256), 0, st, P->hv, (uint32_t)R, P->pcount);
     size_t tb = P->tmp_cap;
     if (rocprim::radix_sort_pairs<PairSortCfg>(P->tmp, tb, P->hk, P->hk2, P->hv, P->hv2, (uint32_t)R, 0, 64, st) != hipSuccess)
-      return -5;
+      return XCG_RC_HIP;
     // latest definer / first GHIT per hash run by scans (f1: run heads, f2: their prefix, r1: first GHIT)
     hipLaunchKernelGGL(pr_dh_heads_kernel, dim3(grid_for(R + 1)), dim3(256), 0, st, (const uint64_t*)P->hk2,
                        (uint32_t)R, P->f1);
-    if (scan_u32(P, P->f1, P->f2, R + 1, st)) return -5;
+    if (scan_u32(P, P->f1, P->f2, R + 1, st)) return XCG_RC_HIP;
     hipLaunchKernelGGL(pr_fill32_kernel, dim3(grid_for(R)), dim3(256), 0, st, P->r1, R, NIL);
     hipLaunchKernelGGL(pr_dh_vals_kernel, dim3(grid_for(R)), dim3(256), 0, st, d, (const uint32_t*)P->hv2,
                        (uint32_t)R, (const uint32_t*)P->f1, (const uint32_t*)P->f2, P->r1);
-    if (scan_max_incl(P, R, st)) return -5;
+    if (scan_max_incl(P, R, st)) return XCG_RC_HIP;
     hipLaunchKernelGGL(pr_dec_hits_kernel, dim3(grid_for(R)), dim3(256), 0, st, d, (const uint32_t*)P->hv2,
                        (uint32_t)R, (const uint32_t*)P->f1, (const uint32_t*)P->f2, (const uint32_t*)P->r1);
   }
@@ -1235,29 +1235,29 @@ int replay(XcgPairState* P, const RowSrc& rs, const HashTab& g, bool want_leave,
     size_t tb = P->tmp_cap;
     if (rocprim::radix_sort_pairs<PairSortCfg>(P->tmp, tb, P->skey, P->sk, P->sval, P->sv, (uint32_t)np, 0, bits, st) !=
         hipSuccess)
-      return -5;
+      return XCG_RC_HIP;
   }
   hipLaunchKernelGGL(pr_fill32_kernel, dim3(grid_for(np)), dim3(256), 0, st, (uint32_t*)P->nxt, np, NIL);
   hipLaunchKernelGGL(pr_link_vals_kernel, dim3(grid_for(np)), dim3(256), 0, st, d);
-  if (scan_max_excl(P, np, st)) return -5;
+  if (scan_max_excl(P, np, st)) return XCG_RC_HIP;
   hipLaunchKernelGGL(pr_links_kernel, dim3(grid_for(np)), dim3(256), 0, st, d);
   if (rs.dec) hipLaunchKernelGGL(pr_repl_links_kernel, dim3(grid_for(np)), dim3(256), 0, st, d);
-  if (scan_u32(P, P->isr, P->rc, np + 1, st)) return -5;
+  if (scan_u32(P, P->isr, P->rc, np + 1, st)) return XCG_RC_HIP;
   hipLaunchKernelGGL(pr_hits_kernel, dim3(grid_for(np)), dim3(256), 0, st, d);
-  if (read_cnt(P, st)) return -5;
+  if (read_cnt(P, st)) return XCG_RC_HIP;
   const uint32_t nslow = P->h_cnt->nslow;
-  if (P->h_cnt->nohit) return -95;
+  if (P->h_cnt->nohit) return XCG_RC_NOTSUP;
   if (nslow) {                                     // the block table for long gaps
     uint32_t bsh = 8;
     while ((np >> bsh) > 1024) ++bsh;
     const uint32_t nbk = (uint32_t)((np + (1ull << bsh) - 1) >> bsh);
     const uint64_t w = (uint64_t)nbk + 1;
     const uint64_t cells = (uint64_t)nbk * w + TSEG * w;
-    if (!P->mem.grow_exact(&P->tab, &P->tab_cap, cells)) return -5;
+    if (!P->mem.grow_exact(&P->tab, &P->tab_cap, cells)) return XCG_RC_HIP;
     d.tab = P->tab;
     d.bsh = bsh;
     d.nbk = nbk;
-    if (hipMemsetAsync(P->tab, 0, 4 * (uint64_t)nbk * w, st) != hipSuccess) return -5;
+    if (hipMemsetAsync(P->tab, 0, 4 * (uint64_t)nbk * w, st) != hipSuccess) return XCG_RC_HIP;
     hipLaunchKernelGGL(pr_tab_hist_kernel, dim3(grid_for(np)), dim3(256), 0, st, d);
     hipLaunchKernelGGL(pr_tab_rows_kernel, dim3((nbk + 3) / 4), dim3(256), 0, st, d);
     uint32_t* segsum = P->tab + (uint64_t)nbk * w;
@@ -1268,24 +1268,24 @@ int replay(XcgPairState* P, const RowSrc& rs, const HashTab& g, bool want_leave,
   }
   // the disk clock: monotone rounds to the least fixed point
   hipLaunchKernelGGL(pr_nq_vals_kernel, dim3(grid_for(np)), dim3(256), 0, st, d);
-  if (scan_min_incl(P, np, st)) return -5;
+  if (scan_min_incl(P, np, st)) return XCG_RC_HIP;
   hipLaunchKernelGGL(pr_nq_kernel, dim3(grid_for(np)), dim3(256), 0, st, d);
-  if (hipMemsetAsync(P->tnew, 0, np + 1, st) != hipSuccess) return -5;
+  if (hipMemsetAsync(P->tnew, 0, np + 1, st) != hipSuccess) return XCG_RC_HIP;
   int rounds = 0;
   for (;; ++rounds) {
-    if (scan_u32(P, P->app, P->clk, np + 1, st)) return -5;
-    if (rounds >= 64) return -75;
-    if (hipMemsetAsync(&P->cnt->changed, 0, 4, st) != hipSuccess) return -5;
+    if (scan_u32(P, P->app, P->clk, np + 1, st)) return XCG_RC_HIP;
+    if (rounds >= 64) return XCG_RC_OVERFLOW;
+    if (hipMemsetAsync(&P->cnt->changed, 0, 4, st) != hipSuccess) return XCG_RC_HIP;
     hipLaunchKernelGGL(pr_touch_chain_kernel, dim3(grid_for(etot)), dim3(256), 0, st, d);
     hipLaunchKernelGGL(pr_setter_vals_kernel, dim3(grid_for(np)), dim3(256), 0, st, d);
-    if (scan_max_excl(P, np, st)) return -5;
+    if (scan_max_excl(P, np, st)) return XCG_RC_HIP;
     hipLaunchKernelGGL(pr_touch_rows_kernel, dim3(grid_for(np)), dim3(256), 0, st, d);
-    if (read_cnt(P, st)) return -5;
+    if (read_cnt(P, st)) return XCG_RC_HIP;
     if (P->h_cnt->changed == 0) break;
   }
   hipLaunchKernelGGL(pr_check_kernel, dim3(grid_for(np)), dim3(256), 0, st, d);
   if (hipMemcpyAsync(P->h_small, P->clk + np, 4, hipMemcpyDeviceToHost, st) != hipSuccess || read_cnt(P, st))
-    return -5;
+    return XCG_RC_HIP;
   out->appends = P->h_small[0];
   out->nbad = P->h_cnt->nbad;
   out->split = P->h_cnt->split != 0 || P->h_cnt->unsorted != 0;
@@ -1299,18 +1299,18 @@ int replay(XcgPairState* P, const RowSrc& rs, const HashTab& g, bool want_leave,
   if (out->split) return 0;
   if (want_leave || out->nbad) {
     hipLaunchKernelGGL(pr_missterm_kernel, dim3(grid_for(np + 1)), dim3(256), 0, st, d);
-    if (scan_u32(P, P->f1, P->r1, np + 1, st) || scan_u32(P, P->f2, P->r2, np + 1, st)) return -5;
+    if (scan_u32(P, P->f1, P->r1, np + 1, st) || scan_u32(P, P->f2, P->r2, np + 1, st)) return XCG_RC_HIP;
     hipLaunchKernelGGL(pr_missrow_kernel, dim3(grid_for(np)), dim3(256), 0, st, d);
-    if (read_small(P, P->r1 + np, 4, st)) return -5;
+    if (read_small(P, P->r1 + np, 4, st)) return XCG_RC_HIP;
     P->last_M = P->h_small[0];
     P->last_ranked = true;
-    if (hipMemsetAsync(&P->cnt->changed, 0, 4, st) != hipSuccess) return -5;
+    if (hipMemsetAsync(&P->cnt->changed, 0, 4, st) != hipSuccess) return XCG_RC_HIP;
     hipLaunchKernelGGL(pr_cover_kernel, dim3(grid_for(newb)), dim3(256), 0, st, d);
     hipLaunchKernelGGL(pr_span_vals_kernel, dim3(grid_for(np)), dim3(256), 0, st, d, P->last_M);
-    if (scan_max_excl(P, np, st)) return -5;
+    if (scan_max_excl(P, np, st)) return XCG_RC_HIP;
     hipLaunchKernelGGL(pr_gaps_kernel, dim3(grid_for(np)), dim3(256), 0, st, d, P->last_M);
     hipLaunchKernelGGL(pr_leave_kernel, dim3(grid_for(newb)), dim3(256), 0, st, d);
-    if (read_cnt(P, st)) return -5;
+    if (read_cnt(P, st)) return XCG_RC_HIP;
     out->changed = P->h_cnt->changed != 0;
   }
   return 0;
@@ -1341,38 +1341,38 @@ int pair_commit(XcgPairState* P, const PairGpu& G, hipStream_t st) {
   XcgDiskState* K = P->disk;
   PairDev d = P->last;
   const uint64_t np = d.np;
-  if (ensure_front_arrays(P)) return -5;
+  if (ensure_front_arrays(P)) return XCG_RC_HIP;
   d.occ = P->occ; d.freel = P->freel; d.lru2 = P->lru2;
   if (!P->last_ranked) {
     hipLaunchKernelGGL(pr_missterm_kernel, dim3(grid_for(np + 1)), dim3(256), 0, st, d);
-    if (scan_u32(P, P->f1, P->r1, np + 1, st) || scan_u32(P, P->f2, P->r2, np + 1, st)) return -5;
+    if (scan_u32(P, P->f1, P->r1, np + 1, st) || scan_u32(P, P->f2, P->r2, np + 1, st)) return XCG_RC_HIP;
     hipLaunchKernelGGL(pr_missrow_kernel, dim3(grid_for(np)), dim3(256), 0, st, d);
     if (P->unbounded) {                            // (only this check needs M on the host)
-      if (read_small(P, P->r1 + np, 4, st)) return -5;
+      if (read_small(P, P->r1 + np, 4, st)) return XCG_RC_HIP;
       P->last_M = P->h_small[0];
     }
   }
   // the primary never evicts: its capacity is exceeded
-  if (P->unbounded && (int64_t)d.P + (int64_t)P->last_M - (int64_t)P->C > 0) return -75;
+  if (P->unbounded && (int64_t)d.P + (int64_t)P->last_M - (int64_t)P->C > 0) return XCG_RC_OVERFLOW;
   const uint64_t dend = K->vol.dclock + P->last_appends;
   if (hipMemsetAsync(P->occ, 0, 4ull * P->C, st) != hipSuccess ||
       hipMemsetAsync(&P->cnt->nmove, 0, 8, st) != hipSuccess)
-    return -5;
+    return XCG_RC_HIP;
   // (terminal ranks r2 are consumed by pr_final before f1 / f2 / r1 / r2 are reused)
   hipLaunchKernelGGL(pr_final_kernel, dim3(grid_for(np + 1)), dim3(256), 0, st, d, (const uint32_t*)P->r1 + np);
-  if (scan_u32(P, P->f1, P->r1, np + 1, st) || scan_u32(P, P->f2, P->r2, np + 1, st)) return -5;
+  if (scan_u32(P, P->f1, P->r1, np + 1, st) || scan_u32(P, P->f2, P->r2, np + 1, st)) return XCG_RC_HIP;
   hipLaunchKernelGGL(pr_notocc_kernel, dim3(grid_for(P->C + 1)), dim3(256), 0, st, (const uint32_t*)P->occ, P->C,
                      P->ofl);
-  if (scan_u32(P, P->ofl, P->ofr, (uint64_t)P->C + 1, st)) return -5;
+  if (scan_u32(P, P->ofl, P->ofr, (uint64_t)P->C + 1, st)) return XCG_RC_HIP;
   hipLaunchKernelGGL(pr_free_kernel, dim3(grid_for(P->C)), dim3(256), 0, st, d, (const uint32_t*)P->ofr);
   hipLaunchKernelGGL(pr_place_kernel, dim3(grid_for(np)), dim3(256), 0, st, d, dend);
   if (d.dec) hipLaunchKernelGGL(pr_remove_kernel, dim3(grid_for(np)), dim3(256), 0, st, d, dend);
   hipLaunchKernelGGL(pr_append_kernel, dim3(grid_for(np)), dim3(256), 0, st, d, dend);
   if (hipMemcpyAsync(P->h_small, P->r1 + np, 4, hipMemcpyDeviceToHost, st) != hipSuccess || read_cnt(P, st))
-    return -5;
+    return XCG_RC_HIP;
   const uint32_t pc = P->h_small[0], nmove = P->h_cnt->nmove, nstage = P->h_cnt->nstage;
-  if (pc > P->C) return -5;
-  if (!P->mem.grow_exact(&P->staging, &P->stg_cap, (uint64_t)std::max<uint32_t>(nstage, 1) * SEG)) return -5;
+  if (pc > P->C) return XCG_RC_HIP;
+  if (!P->mem.grow_exact(&P->staging, &P->stg_cap, (uint64_t)std::max<uint32_t>(nstage, 1) * SEG)) return XCG_RC_HIP;
   if (nmove) {
     hipLaunchKernelGGL(pair_stage_kernel, dim3((nmove + 3) / 4), dim3(256), 0, st, (const uint4*)P->moves,
                        (const PairCnt*)P->cnt, (const uint8_t*)G.g.pool, P->staging);
@@ -1386,12 +1386,12 @@ int pair_commit(XcgPairState* P, const PairGpu& G, hipStream_t st) {
   volume_advance(&K->vol, P->last_appends);          // (the clock is now dend)
   P->appends = P->last_appends;
   pair_rebuild(P, G, st);
-  return hipStreamSynchronize(st) == hipSuccess && hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipStreamSynchronize(st) == hipSuccess && hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
 }
 
 int fill_ptime(XcgPairState* P, hipStream_t st) {
   hipLaunchKernelGGL(pr_fill64_kernel, dim3(1024), dim3(256), 0, st, P->ptime, (uint64_t)P->C + P->D, NEVERT);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
 }
 
 // Entries another front's writes retired (the clock crossed an index block
@@ -1400,7 +1400,7 @@ int pair_sync_front(XcgPairState* P, const PairGpu& G, hipStream_t st) {
   XcgDiskState* K = P->disk;
   if (!P->gstale && K->vol.dclock / DISK_ENTRIES == P->gclock / DISK_ENTRIES) return 0;
   pair_rebuild(P, G, st);
-  return hipStreamSynchronize(st) == hipSuccess && hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipStreamSynchronize(st) == hipSuccess && hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
 }
 
 PairGpu gpu_of(const XcgStreamArgs& a) {
@@ -1425,8 +1425,8 @@ int xcg_pair_decode_begin(XcgPairState* P, hipStream_t st) { return fill_ptime(P
 // d_base[c], d_cnt[c] of them; `rows` total).  *same = the departure times it
 // computes equal those the classification used (then it was the sequential
 // decoder's).  Otherwise ptime is updated for the next classification.
-// Returns 0, -95 (a batch the pair model declines: a hash this batch named
-// gone before a later lookup, more than a disk lap of writes), -5.
+// Returns 0, XCG_RC_NOTSUP (a batch the pair model declines: a hash this batch named
+// gone before a later lookup, more than a disk lap of writes), XCG_RC_HIP.
 int xcg_pair_decode_pass(XcgPairState* P, const PairGpu* G, const void* d_rows, const uint64_t* d_base,
                          const uint64_t* d_cnt, uint32_t n, uint64_t rows, uint32_t maxd, int* same, hipStream_t st) {
   RowSrc rs{1, n, maxd, (const uint4*)d_rows, nullptr, 0u, d_base, d_cnt, rows, nullptr, nullptr, nullptr};
@@ -1434,7 +1434,7 @@ int xcg_pair_decode_pass(XcgPairState* P, const PairGpu* G, const void* d_rows, 
   const HashTab g = tab_of(G->g);
   const int rc = replay(P, rs, g, true, &o, st);
   if (rc) return rc;
-  if (o.split) return -95;
+  if (o.split) return XCG_RC_NOTSUP;
   *same = !o.changed;
   return 0;
 }
@@ -1443,17 +1443,17 @@ int xcg_pair_decode_pass(XcgPairState* P, const PairGpu* G, const void* d_rows, 
 // declaration rows: G.decl[c * maxd + d].z = the EXTRACT payload's offset).
 int xcg_pair_decode_commit(XcgPairState* P, const PairGpu* G, hipStream_t st) {
   const int rc = pair_commit(P, *G, st);
-  if (fill_ptime(P, st)) return -5;
+  if (fill_ptime(P, st)) return XCG_RC_HIP;
   return rc;
 }
 
 // Stream-semantics encode of a batch on the pair, in sub-batches (see the top
-// of this file).  Returns 0, -75 (no consistent pass / overflow), -95 (one
-// chunk alone exceeds what a sub-batch may hold), -5.
+// of this file).  Returns 0, XCG_RC_OVERFLOW (no consistent pass / overflow), XCG_RC_NOTSUP (one
+// chunk alone exceeds what a sub-batch may hold), XCG_RC_HIP.
 int xcg_pair_encode_stream(const XcgStreamArgs* a0, XcgPairState* P, int* rounds_out, hipStream_t st) {
   const uint32_t n = a0->n;
   int rounds = 0;
-  if (pair_sync_front(P, gpu_of(*a0), st)) return -5;
+  if (pair_sync_front(P, gpu_of(*a0), st)) return XCG_RC_HIP;
   // A sub-batch is bounded by the disk only: while it writes fewer than a lap
   // of disk blocks, nothing it declared can leave both levels within it (a
   // chunk writes at most maxd declarations plus its touches).
@@ -1490,7 +1490,7 @@ int xcg_pair_encode_stream(const XcgStreamArgs* a0, XcgPairState* P, int* rounds
     StreamTemp flags_tmp(st);                        // (freed on `st` when the sub-batch is done, or fails)
     uint32_t* scratch_flags = nullptr;
     if (!a.bad_t) {                                  // (no restart arrays: flags into scratch)
-      if (!flags_tmp.alloc(&scratch_flags, 8ull * m)) return -5;
+      if (!flags_tmp.alloc(&scratch_flags, 8ull * m)) return XCG_RC_HIP;
       rs.bad_t = scratch_flags;
       rs.bad_hi = scratch_flags + m;
     }
@@ -1499,7 +1499,7 @@ int xcg_pair_encode_stream(const XcgStreamArgs* a0, XcgPairState* P, int* rounds
     // one pass: then the first guess is the tiling seed's own references,
     // replayed (a cached tile is a lookup hit, a repeat of an earlier tile a hit
     // on its declaration, every other tile a declaration).
-    if (xcg_launch_seed_tiling(&a, st)) return -5;
+    if (xcg_launch_seed_tiling(&a, st)) return XCG_RC_HIP;
     const clk::time_point t1 = clk::now();
     if (P->prev_passes > 1) {
       const HashTab b{a.b_keys, a.b_vals, a.b_mask};
@@ -1515,7 +1515,7 @@ int xcg_pair_encode_stream(const XcgStreamArgs* a0, XcgPairState* P, int* rounds
         hipLaunchKernelGGL(pair_seed_events_kernel, dim3((m + 3) / 4), dim3(256), 0, st, m, (const uint4*)a.decl,
                            (const uint32_t*)a.ndecl, a.maxd, a.chunk_len, g, b, (uint4*)a.ev, a.nev, a.maxe,
                            it ? (const uint64_t*)P->ptime : nullptr);
-        if (!clear_flags()) return -5;
+        if (!clear_flags()) return XCG_RC_HIP;
         PassOut o;
         const int rc = replay(P, rs, g, true, &o, st);
         if (rc) return rc;
@@ -1537,10 +1537,10 @@ int xcg_pair_encode_stream(const XcgStreamArgs* a0, XcgPairState* P, int* rounds
       if (rc) return rc;
       if (pair_debug()) (void)hipStreamSynchronize(st);
       const clk::time_point q1 = clk::now();
-      if (!clear_flags()) return -5;
+      if (!clear_flags()) return XCG_RC_HIP;
       PassOut o;
       const int prc = replay(P, rs, g, false, &o, st);
-      if (prc == -75) { split = true; break; }
+      if (prc == XCG_RC_OVERFLOW) { split = true; break; }
       if (prc) return prc;
       const clk::time_point q2 = clk::now();
       t_parse += ms(q0, q1);
@@ -1553,22 +1553,22 @@ int xcg_pair_encode_stream(const XcgStreamArgs* a0, XcgPairState* P, int* rounds
       // else: the replay flagged the chunks (need / bad_t / bad_hi) and set ptime
     }
     if (!done) {
-      if (m == 1) return split ? -95 : -75;
+      if (m == 1) return split ? XCG_RC_NOTSUP : XCG_RC_OVERFLOW;
       per = m / 2;                                 // redo this part in halves
       P->fit_per = 0;                              // (and size the next call from the worst case again)
       P->prev_passes = MAX_PASSES;
-      if (fill_ptime(P, st)) return -5;
+      if (fill_ptime(P, st)) return XCG_RC_HIP;
       continue;
     }
     const clk::time_point t3 = clk::now();
     const PairGpu G = gpu_of(a);
-    if (const int crc = pair_commit(P, G, st)) return crc == -75 ? -75 : -5;
+    if (const int crc = pair_commit(P, G, st)) return crc == XCG_RC_OVERFLOW ? XCG_RC_OVERFLOW : XCG_RC_HIP;
     if (pair_debug())
       fprintf(stderr, "pair: ms seed %.2f seed-replay %.2f parse %.2f replay %.2f commit %.2f (primary %u, clock %llu)\n",
               ms(t0, t1), ms(t1, t2), t_parse, t_replay, ms(t3, clk::now()), P->pcount,
               (unsigned long long)P->disk->vol.dclock);
     // the next sub-batch starts with every hash visible to its end
-    if (fill_ptime(P, st)) return -5;
+    if (fill_ptime(P, st)) return XCG_RC_HIP;
     P->last_base = i0;
     P->prev_passes = passes;
     i0 += m;
@@ -1582,7 +1582,7 @@ int xcg_pair_encode_stream(const XcgStreamArgs* a0, XcgPairState* P, int* rounds
     per = (uint32_t)(want < 1 ? 1 : (want > n ? n : want));
   }
   if (rounds_out) *rounds_out = rounds;
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
 }
 
 }  // extern "C"

@@ -52,7 +52,7 @@ int ensure_front_arrays(XcgPairState* P) {
   DevMem& m = P->mem;
   return m.dev(&P->occ, 4ull * P->C) && m.dev(&P->freel, 4ull * P->C) && m.dev(&P->ofl, 4ull * (P->C + 1)) &&
                  m.dev(&P->ofr, 4ull * (P->C + 1))
-             ? 0 : -5;
+             ? 0 : XCG_RC_HIP;
 }
 
 }  // namespace xcg
@@ -63,7 +63,7 @@ using namespace xcg;
 
 // The disk's device arrays, on the first front's device.
 int disk_bind(XcgDiskState* K, int device) {
-  if (K->device >= 0) return K->device == device ? 0 : -22;
+  if (K->device >= 0) return K->device == device ? 0 : XCG_RC_INVAL;
   const uint64_t D = K->vol.D;
   if (!(K->mem.dev(&K->dkey, 8 * D) && K->mem.dev(&K->dent, 8 * D) && K->mem.dev(&K->dxuid, 4 * D)) ||
       hipMemset(K->dkey, 0xFF, 8 * D) != hipSuccess ||
@@ -71,7 +71,7 @@ int disk_bind(XcgDiskState* K, int device) {
     K->mem.release_all();
     K->dkey = K->dent = nullptr;
     K->dxuid = nullptr;
-    return -12;
+    return XCG_RC_NOMEM;
   }
   K->device = device;
   return 0;
@@ -183,7 +183,7 @@ int map_pool(XcgPairState* P, int device) {
     P->va = nullptr;
     (void)hipGetLastError();
   }
-  if (!P->mem.dev(&P->pool, ((uint64_t)P->C + P->D) * SEG + 256)) return -12;
+  if (!P->mem.dev(&P->pool, ((uint64_t)P->C + P->D) * SEG + 256)) return XCG_RC_NOMEM;
   P->pool_vmm = false;
   return 0;
 }
@@ -218,8 +218,8 @@ int read_disk_blocks(const XcgDiskState* K, uint8_t* dst) {
   const uint8_t* src = (const uint8_t*)K->dva;
   for (const XcgPairState* f : K->fronts)            // (no mapping of its own: a live front's)
     if (!src && f) src = f->pool + (uint64_t)f->C * SEG;
-  if (!src) return -5;
-  return hipMemcpy(dst, src, (size_t)K->vol.D * SEG, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -5;
+  if (!src) return XCG_RC_HIP;
+  return hipMemcpy(dst, src, (size_t)K->vol.D * SEG, hipMemcpyDeviceToHost) == hipSuccess ? 0 : XCG_RC_HIP;
 }
 
 }  // namespace
@@ -275,11 +275,11 @@ int xcg_pair_state_unbounded(const XcgPairState* P) { return P && P->unbounded ?
 // A pair front on disk K, on the current device.  Which front (xuid) it is:
 // volume_front_xuid.  The registry entry is written once the front exists.
 int xcg_pair_state_create(uint32_t C, XcgDiskState* K, const char* uuid36, int want_xuid, XcgPairState** out) {
-  if (C == 0 || !K || (uint64_t)K->vol.D + C >= (1ull << 30)) return -22;
-  if (uuid36 && (strlen(uuid36) != 36 || !uuid_ok((const uint8_t*)uuid36))) return -22;
-  if (want_xuid >= (int)XUIDS) return -22;
+  if (C == 0 || !K || (uint64_t)K->vol.D + C >= (1ull << 30)) return XCG_RC_INVAL;
+  if (uuid36 && (strlen(uuid36) != 36 || !uuid_ok((const uint8_t*)uuid36))) return XCG_RC_INVAL;
+  if (want_xuid >= (int)XUIDS) return XCG_RC_INVAL;
   int device = 0;
-  if (hipGetDevice(&device) != hipSuccess) return -5;
+  if (hipGetDevice(&device) != hipSuccess) return XCG_RC_HIP;
   auto bound = [&](uint32_t x) { return x < K->fronts.size() && K->fronts[x] != nullptr; };
   std::string name;
   const int xrc = volume_front_xuid(K->vol, uuid36, want_xuid, bound, &name);
@@ -306,12 +306,12 @@ int xcg_pair_state_create(uint32_t C, XcgDiskState* K, const char* uuid36, int w
         m.dev(&P->lru2, 4ull * C) && m.dev(&P->ptime, 8 * ids) && m.dev(&P->erep, 4 * ids)) ||
       hipMemset(P->pkey, 0xFF, 8ull * C) != hipSuccess || hipMemset(P->pdisk, 0xFF, 8ull * C) != hipSuccess ||
       hipMemset(P->ptime, 0xFF, 8 * ids) != hipSuccess || ensure_front_arrays(P) != 0 || map_pool(P, device) != 0)
-    return fail(-12);
+    return fail(XCG_RC_NOMEM);
   uint8_t* blocks = P->pool + (uint64_t)C * SEG;
   Volume& V = K->vol;
   const uint64_t D = V.D;
   if (!K->pending && !K->zeroed) {
-    if (hipMemset(blocks, 0, D * SEG) != hipSuccess) return fail(-5);
+    if (hipMemset(blocks, 0, D * SEG) != hipSuccess) return fail(XCG_RC_HIP);
     K->zeroed = K->vmm;
   }
   if (K->pending) {                                         // a reopened volume's ring and blocks
@@ -319,15 +319,15 @@ int xcg_pair_state_create(uint32_t C, XcgDiskState* K, const char* uuid36, int w
         (hipMemcpy(K->dkey, V.h_key.data(), 8 * D, hipMemcpyHostToDevice) != hipSuccess ||
          hipMemcpy(K->dent, V.h_ent.data(), 8 * D, hipMemcpyHostToDevice) != hipSuccess ||
          hipMemcpy(K->dxuid, V.h_xuid.data(), 4 * D, hipMemcpyHostToDevice) != hipSuccess))
-      return fail(-5);
+      return fail(XCG_RC_HIP);
     K->ring_loaded = true;
-    if (hipMemcpy(blocks, V.h_data.data(), D * SEG, hipMemcpyHostToDevice) != hipSuccess) return fail(-5);
+    if (hipMemcpy(blocks, V.h_data.data(), D * SEG, hipMemcpyHostToDevice) != hipSuccess) return fail(XCG_RC_HIP);
   }
   if (!P->pool_vmm && !K->shadow_ok.empty()) {               // blocks of fronts that went away
     for (uint64_t i = 0; i < D; ++i)
       if (K->shadow_ok[i] &&
           hipMemcpy(blocks + i * SEG, &K->shadow[i * SEG], SEG, hipMemcpyHostToDevice) != hipSuccess)
-        return fail(-5);
+        return fail(XCG_RC_HIP);
   }
   if (K->pending && K->vmm) {                                // (one copy serves every front)
     K->pending = false;
@@ -370,9 +370,9 @@ int xcg_disk_state_save(XcgDiskState* K, const char* path) {
     if (hipDeviceSynchronize() != hipSuccess ||
         hipMemcpy(key.data(), K->dkey, 8 * D, hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(xu.data(), K->dxuid, 4 * D, hipMemcpyDeviceToHost) != hipSuccess)
-      return -5;
+      return XCG_RC_HIP;
     if (K->vmm) {
-      if (read_disk_blocks(K, data.data())) return -5;
+      if (read_disk_blocks(K, data.data())) return XCG_RC_HIP;
     } else {
       // per-front copies: a block comes from the live front that wrote it,
       // else from what a front that went away left, else from the volume
@@ -383,7 +383,7 @@ int xcg_disk_state_save(XcgDiskState* K, const char* path) {
       for (XcgPairState* f : K->fronts) {
         if (!f) continue;
         if (hipMemcpy(tmp.data(), f->pool + (uint64_t)f->C * SEG, D * SEG, hipMemcpyDeviceToHost) != hipSuccess)
-          return -5;
+          return XCG_RC_HIP;
         for (uint64_t i = 0; i < D; ++i)
           if (xu[i] == f->xuid) memcpy(&data[i * SEG], &tmp[i * SEG], SEG);
       }
@@ -402,12 +402,12 @@ int xcg_disk_state_open_fd(int fd, uint64_t disk_bytes, uint32_t flags, XcgDiskS
   struct stat st;
   if (fstat(fd, &st) != 0) {
     delete K;
-    return -2;
+    return XCG_RC_NOENT;
   }
   if (st.st_size > 0) {
     if (volume_load(&K->vol, fd) != 0) {
       delete K;
-      return -2;
+      return XCG_RC_NOENT;
     }
     K->pending = true;
   }
@@ -420,7 +420,7 @@ int xcg_disk_state_open(const char* path, uint64_t disk_bytes, uint32_t flags, X
   const int fd = ::open(path, O_RDONLY);
   if (fd == -1) {
     if (errno == ENOENT) return xcg_disk_state_create(disk_bytes, flags, out);
-    return -2;
+    return XCG_RC_NOENT;
   }
   const int rc = xcg_disk_state_open_fd(fd, disk_bytes, flags, out);
   close(fd);
@@ -473,7 +473,7 @@ int xcg_pair_state_clear(XcgPairState* P) {
   uint64_t others = 0;
   for (const XcgPairState* f : K->fronts) others += f && f != P;
   if (hipMemset(P->pkey, 0xFF, 8ull * P->C) != hipSuccess || hipMemset(P->pdisk, 0xFF, 8ull * P->C) != hipSuccess)
-    return -5;
+    return XCG_RC_HIP;
   hipLaunchKernelGGL(pair_drop_front_kernel, dim3(grid_for(K->vol.D)), dim3(256), 0, nullptr, K->dkey, K->dent,
                      (const uint32_t*)K->dxuid, K->vol.D, others ? (uint32_t)P->xuid : NIL);
   if (!others) volume_reset(&K->vol);                        // a fresh volume
@@ -481,7 +481,7 @@ int xcg_pair_state_clear(XcgPairState* P) {
   P->gclock = K->vol.dclock;
   P->gstale = false;
   P->prev_passes = 1;
-  return hipDeviceSynchronize() == hipSuccess ? 0 : -5;
+  return hipDeviceSynchronize() == hipSuccess ? 0 : XCG_RC_HIP;
 }
 
 void xcg_pair_state_stats(const XcgPairState* P, uint64_t* st) {

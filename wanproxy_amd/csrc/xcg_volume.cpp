@@ -17,9 +17,9 @@ namespace xcg {
 
 int volume_geometry(Volume* V, uint64_t disk_bytes) {
   const uint64_t blocks = disk_bytes / SEG;
-  if (blocks <= 18) return -22;
+  if (blocks <= 18) return XCG_RC_INVAL;
   const uint64_t nb = (blocks - 18) / (1 + DISK_ENTRIES);   // xcodec_cache_disk.cc:110-111
-  if (nb == 0 || nb * DISK_ENTRIES >= (1ull << 29)) return -22;
+  if (nb == 0 || nb * DISK_ENTRIES >= (1ull << 29)) return XCG_RC_INVAL;
   V->nb = nb;
   V->D = (uint32_t)(nb * DISK_ENTRIES);
   V->bytes = disk_bytes;
@@ -119,7 +119,7 @@ int volume_load(Volume* V, int fd) {
   if (!pread_all(fd, vol.data(), vol.size(), 0) ||
       !pread_all(fd, V->h_data.data(), V->h_data.size(), (off_t)vol.size())) {
     std::vector<uint8_t>().swap(V->h_data);
-    return -2;
+    return XCG_RC_NOENT;
   }
   memcpy(&V->reg[0], &vol[0], V->reg.size());
   std::unordered_map<std::string, uint32_t> seen;
@@ -135,7 +135,7 @@ int volume_load(Volume* V, int fd) {
   }
   if (seen.empty()) {                                       // registry_load: a local UUID (:575-596)
     char u[37];
-    if (!gen_uuid(u)) return -2;
+    if (!gen_uuid(u)) return XCG_RC_NOENT;
     V->uuid[0] = std::string(u, 36);
     registry_write(V, 0, u);
   }
@@ -232,7 +232,7 @@ int volume_load(Volume* V, int fd) {
 int volume_write(const Volume& V, const char* path, const uint64_t* key, const uint32_t* xu, const uint8_t* data) {
   const uint64_t nb = V.nb, D = V.D;
   const int fd = ::open(path, O_RDWR | O_CREAT | O_TRUNC, 0600);
-  if (fd == -1) return -2;
+  if (fd == -1) return XCG_RC_NOENT;
   bool ok = ftruncate(fd, (off_t)V.bytes) == 0;
   ok = ok && pwrite_all(fd, V.reg.data(), V.reg.size(), 0);
   std::vector<uint8_t> ib(2048);
@@ -254,7 +254,7 @@ int volume_write(const Volume& V, const char* path, const uint64_t* key, const u
   }
   ok = ok && pwrite_all(fd, data, (size_t)D * SEG, (off_t)((REG_BLOCKS + nb) * 2048));
   close(fd);
-  return ok ? 0 : -5;
+  return ok ? 0 : XCG_RC_HIP;
 }
 
 // `appends` more entries written: index blocks the write head leaves are
@@ -300,22 +300,22 @@ int volume_front_xuid(const Volume& V, const char* uuid36, int want_xuid, const 
     for (uint32_t x = 0; x < XUIDS; ++x)
       if (V.uuid[x] == uuid36) { xuid = x; break; }
   if (want_xuid >= 0) {
-    if (xuid < XUIDS && xuid != (uint32_t)want_xuid) return -22;
+    if (xuid < XUIDS && xuid != (uint32_t)want_xuid) return XCG_RC_INVAL;
     xuid = (uint32_t)want_xuid;
   } else if (!uuid36 && !V.uuid[0].empty() && !bound(0)) {
     xuid = 0;
   }
-  if (xuid < XUIDS && bound(xuid)) return -22;               // (one engine front per disk front)
+  if (xuid < XUIDS && bound(xuid)) return XCG_RC_INVAL;               // (one engine front per disk front)
   if (xuid >= XUIDS)
     for (xuid = 0; xuid < XUIDS && (bound(xuid) || !V.uuid[xuid].empty()); ++xuid) {
     }
-  if (xuid >= XUIDS) return -22;                            // XCDFS_XUID_COUNT
+  if (xuid >= XUIDS) return XCG_RC_INVAL;                            // XCDFS_XUID_COUNT
   name->clear();
   if (uuid36) {
     name->assign(uuid36, 36);
   } else if (V.uuid[xuid].empty()) {
     char gen[37];
-    if (!gen_uuid(gen)) return -5;
+    if (!gen_uuid(gen)) return XCG_RC_HIP;
     name->assign(gen, 36);
   }
   return (int)xuid;

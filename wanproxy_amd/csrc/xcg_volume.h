@@ -13,6 +13,8 @@
 #include <string>
 #include <vector>
 
+#include "xcg_rc.h"
+
 namespace xcg {
 
 constexpr uint32_t DISK_ENTRIES = 204;   // XCDFS_ENTRIES_PER_INDEX_BLOCK, xcodec_cache_disk.cc:87
@@ -40,12 +42,12 @@ struct Volume {
   std::vector<uint8_t> h_data;
 };
 
-// A fresh volume of disk_bytes.  -22: no room for the registry and one index block, or too many data blocks.
+// A fresh volume of disk_bytes.  XCG_RC_INVAL: no room for the registry and one index block, or too many data blocks.
 int volume_geometry(Volume* V, uint64_t disk_bytes);
-// The reload of a volume file (geometry set).  0, or -2: the file cannot be read.
+// The reload of a volume file (geometry set).  0, or XCG_RC_NOENT: the file cannot be read.
 int volume_load(Volume* V, int fd);
 // The file as the reference's stands now, from the ring's key[D], xuid[D] and data[D * 2048].
-// 0, -2: the path cannot be opened, -5: a write failed.
+// 0, XCG_RC_NOENT: the path cannot be opened, XCG_RC_HIP: a write failed.
 int volume_write(const Volume& V, const char* path, const uint64_t* key, const uint32_t* xuid, const uint8_t* data);
 void volume_advance(Volume* V, uint64_t appends);
 void volume_reset(Volume* V);
@@ -53,7 +55,8 @@ void volume_head(const Volume& V, uint64_t* index_block, uint64_t* next);
 
 void registry_write(Volume* V, uint32_t xuid, const char* u36);
 // Which xuid a new front takes, bound(x) telling the xuids that have a front;
-// *name: the UUID to register for it (empty: the one it has).  -22: none, -5: no UUID could be generated.
+// *name: the UUID to register for it (empty: the one it has).  XCG_RC_INVAL: none,
+// XCG_RC_HIP: no UUID could be generated.
 int volume_front_xuid(const Volume& V, const char* uuid36, int want_xuid, const std::function<bool(uint32_t)>& bound,
                       std::string* name);
 void volume_register(Volume* V, uint32_t xuid, const std::string& name);
