@@ -161,6 +161,95 @@ void case_fits() {
   puts("ok fits");
 }
 
+// The result words of one per-call decode launch, as decode_small_kernel
+// leaves them: in a heap buffer of exactly SD_RES_WORDS words.
+struct Results {
+  std::vector<uint64_t> w;
+  Results() : w(xcg::SD_RES_WORDS, 0) {}
+};
+struct CallOut {
+  uint64_t count = 100, out_len = S64, consumed = S64;
+  int32_t status = (int32_t)S32;
+  uint32_t nunknown = S32, nextract = S32;
+  std::vector<uint8_t> out;
+  std::vector<uint64_t> unknown, extract;
+  CallOut(size_t outb, uint32_t ucap, uint32_t ecap) : out(outb, 0xA5), unknown(ucap + 2, S64), extract(ecap + 2, S64) {}
+  int run(const Results& r, const std::vector<uint8_t>& h_o, uint32_t ucap, uint32_t ecap) {
+    return decode_call_results(&count, r.w.data(), h_o.data(), out.data(), &out_len, &consumed, &status, unknown.data(),
+                               ucap, &nunknown, extract.data(), ecap, &nextract);
+  }
+  bool untouched() const {
+    for (uint8_t b : out) if (b != 0xA5) return false;
+    for (uint64_t v : unknown) if (v != S64) return false;
+    for (uint64_t v : extract) if (v != S64) return false;
+    return count == 100 && consumed == S64 && status == (int32_t)S32 && nunknown == S32 && nextract == S32;
+  }
+};
+
+void case_results() {
+  using namespace xcg;
+  CHECK(SD_RES_UNKNOWN == 8 && SD_RES_EXTRACT == 8 + 2048 && SD_RES_STICKY == 8 + 2048 + 1024 &&
+        SD_RES_WORDS == SD_RES_STICKY + 1);
+  const std::vector<uint8_t> h_o = {1, 2, 3, 4, 5};
+  {  // fallback 1: the batch path takes it, nothing written
+    Results r;
+    r.w[SDR_FALLBACK] = SD_FB_BATCH;
+    r.w[SDR_OUT_LEN] = 5; r.w[SDR_DECLARES] = 3; r.w[SDR_UNKNOWNS] = 2; r.w[SDR_EXTRACTS] = 1;
+    CallOut o(5, 4, 4);
+    CHECK(o.run(r, h_o, 4, 4) == XCG_ENOTSUP);
+    CHECK(o.untouched() && o.out_len == S64);
+  }
+  {  // fallback 2: more room needed, the size reported and nothing else
+    Results r;
+    r.w[SDR_FALLBACK] = SD_FB_ROOM;
+    r.w[SDR_NEED] = 4098;
+    CallOut o(5, 4, 4);
+    CHECK(o.run(r, h_o, 4, 4) == XCG_EOVERFLOW);
+    CHECK(o.out_len == 4098 && o.untouched());
+  }
+  {  // the sticky word set: the cache is full, whatever else the words say
+    Results r;
+    r.w[SD_RES_STICKY] = 4;
+    r.w[SDR_OUT_LEN] = 5;
+    CallOut o(5, 4, 4);
+    CHECK(o.run(r, h_o, 4, 4) == XCG_EOVERFLOW);
+    CHECK(o.untouched() && o.out_len == S64);
+    r.w[SD_RES_STICKY] = 1ull << 32;                          // (only the word's low half is the status)
+    CHECK(o.run(r, h_o, 4, 4) == XCG_OK);
+  }
+  // unknown hashes: sorted, cut at the cap -- below, at and above the count
+  const uint64_t unk[3] = {0x30, 0x10, 0x20};
+  for (uint32_t cap : {2u, 3u, 5u}) {
+    Results r;
+    r.w[SDR_OUT_LEN] = 5; r.w[SDR_CONSUMED] = 77; r.w[SDR_STATUS] = (uint64_t)(int64_t)-1; r.w[SDR_DECLARES] = 3;
+    r.w[SDR_UNKNOWNS] = 3;
+    for (int i = 0; i < 3; ++i) r.w[SD_RES_UNKNOWN + i] = unk[i];
+    CallOut o(5, cap, 4);
+    CHECK(o.run(r, h_o, cap, 4) == XCG_OK);
+    CHECK(o.out == h_o && o.out_len == 5 && o.consumed == 77 && o.status == -1 && o.count == 103);
+    const uint32_t k = cap < 3 ? cap : 3;
+    CHECK(o.nunknown == k);
+    for (uint32_t i = 0; i < cap + 2; ++i) CHECK(o.unknown[i] == (i < k ? 0x10u * (i + 1) : S64));
+    CHECK(o.nextract == 0);
+  }
+  // EXTRACT hashes: delivered when the count fits the caller's cap and SD_EMAX
+  for (uint32_t ne : {0u, 3u, 4u, SD_EMAX, SD_EMAX + 1}) {
+    for (uint32_t cap : {3u, SD_EMAX + 2}) {
+      Results r;
+      r.w[SDR_EXTRACTS] = ne;
+      for (uint32_t i = 0; i < SD_EMAX; ++i) r.w[SD_RES_EXTRACT + i] = 0xE000 + i;
+      CallOut o(5, 4, cap);
+      o.nextract = XCG_NO_REFERENCES;
+      CHECK(o.run(r, h_o, 4, cap) == XCG_OK);
+      const bool fits = ne <= cap && ne <= SD_EMAX;
+      CHECK(o.nextract == (fits ? ne : XCG_NO_REFERENCES));
+      for (uint32_t i = 0; i < cap + 2; ++i) CHECK(o.extract[i] == (fits && i < ne ? 0xE000u + i : S64));
+      CHECK(o.out_len == 0 && o.nunknown == 0);
+    }
+  }
+  puts("ok results");
+}
+
 }  // namespace
 
 int main() {
@@ -169,5 +258,6 @@ int main() {
   case_decl_rows();
   case_ref_rows();
   case_fits();
+  case_results();
   return 0;
 }

@@ -33,6 +33,7 @@ def test_harness_exits_clean(harness_run):
     'decl_rows',  # counts 0, 1, 3; cap below, at, above; each output null in turn; nothing written past the cap
     'ref_rows',   # sorted by time, ties in row order; kind / index split at bit 30; the cap applies after the sort
     'fits',       # the fresh-cache predicate at and above the limit and on an unlimited context; the three bounds
+    'results',    # the per-call decoder's result words: fallback 1 / 2, the sticky word, unknown and EXTRACT caps
 ])
 def test_case(harness_run, case):
     assert f'ok {case}' in harness_run.stdout.split('\n'), harness_run.stderr

@@ -104,3 +104,45 @@ def test_backref_empty_window_is_an_error():
     outs, st, cons, _ = ctx.decode_chunks([b'abc\xf1\x03\x07tail', b'next'])
     assert int(st[0]) == -1 and int(cons[0]) == 6 and outs[0] == b'abc'
     assert int(st[1]) == 2
+
+
+def test_backref_after_a_ref_run_longer_than_a_wave(oracle):
+    """The declares a BACKREF sees are counted over runs of REFs: 70
+    consecutive REFs (more than one wave's run of 64) against a warm cache,
+    then BACKREFs into the run on both sides of lane 63; in the next chunk a
+    BACKREF to a slot no declare has reached stops the stream in front of a
+    truncated REF; a following batch reads the window that is left."""
+    import struct
+
+    import numpy as np
+    from wanproxy_amd.xcgpu import Context
+    segs = np.random.default_rng(0xB4C).integers(0, 256, 70 * 2048, dtype=np.uint8).tobytes()
+    ctx = Context(0)
+    hs = [int(h) for h in ctx.cache_learn(segs)]
+    assert len(set(hs)) == 70
+    ref = [b'\xf1\x02' + struct.pack('>Q', h) for h in hs]
+    bref = lambda slot: b'\xf1\x03' + bytes([slot])
+    encs = [b''.join(ref) + bref(2) + bref(68) + b'literal tail',
+            ref[5] + ref[6] + bref(200) + ref[7][:6]]
+    after = [bref(2) + bref(68)]
+    cache = oracle.cache_new()
+    odec = oracle.decoder_new(cache)
+    try:
+        # (warmed through a decoder of its own, so the one under test starts with an empty window)
+        assert oracle.decode(b''.join(b'\xf1\x01' + segs[2048 * k:2048 * (k + 1)] for k in range(70)), cache)[0]
+        want = [oracle.decode(e, cache, decoder=odec) for e in encs + after]
+    finally:
+        oracle.decoder_free(odec)
+        oracle.cache_free(cache)
+    assert [w[0] for w in want] == [True, False, True]       # (the reference's own verdicts)
+    assert want[0][1] == segs + segs[2 * 2048:3 * 2048] + segs[68 * 2048:69 * 2048] + b'literal tail'
+    outs, st, cons, unk = ctx.decode_chunks(encs)
+    assert unk == []
+    assert [int(s) for s in st] == [0, -1]
+    for k in range(2):
+        assert outs[k] == want[k][1] and int(cons[k]) == want[k][2], k
+    outs, st, cons, unk = ctx.decode_chunks(after)
+    assert unk == [] and int(st[0]) == 0
+    assert outs[0] == want[2][1] and int(cons[0]) == want[2][2]
+    assert outs[0] == segs[2 * 2048:3 * 2048] + segs[68 * 2048:69 * 2048]
+    ctx.close()

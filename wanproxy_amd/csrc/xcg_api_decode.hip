@@ -84,12 +84,12 @@ int decode_batch_impl(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_chunk_
   // status word and the declare count, by async copies into pinned memory
   // (a synchronous 4-byte hipMemcpy costs milliseconds here)
   if (hipMemcpyAsync(c->h_status, c->d_status, 4, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
-      hipMemcpyAsync(c->ds.h_scratch + 7, c->ds.scratch + 6, 8, hipMemcpyDeviceToHost, (hipStream_t)stream) !=
-          hipSuccess ||
+      hipMemcpyAsync(&c->ds.h_scratch->t_end, &c->ds.scratch->t_end, 8, hipMemcpyDeviceToHost,
+                     (hipStream_t)stream) != hipSuccess ||
       hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
     return XCG_EHIP;
   const int32_t st = *c->h_status;
-  const uint64_t t_end = c->ds.h_scratch[7];
+  const uint64_t t_end = c->ds.h_scratch->t_end;
   if (!c->no_window) w->count += t_end;               // declares made: the window cursor advances
   if (st & (1 << 9)) {
     (void)hipMemsetAsync(c->d_status, 0, 4, (hipStream_t)stream);
@@ -188,8 +188,8 @@ int xcg_decode_batch_grouped(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d
 
 int xcg_debug_decode_reuse(xcg_ctx* c, uint64_t out[3]) {
   if (!c || !out) return XCG_EINVAL;
-  const uint64_t* h = c->ds.h_scratch;
-  for (int k = 0; k < 3; ++k) out[k] = h ? h[12 + k] : 0;
+  const xcg::DecHostWords* h = c->ds.h_scratch;
+  for (int k = 0; k < 3; ++k) out[k] = h ? h->reuse[k] : 0;
   return XCG_OK;
 }
 
@@ -283,49 +283,16 @@ bool getenv_flag_no_zc() {
   return off;
 }
 
-// The results words of one decode_small_kernel launch -> the call's outputs.
-// XCG_ENOTSUP: the kernel declined (fallback); nothing was written.
-int decode_call_results(xcg_window* w, const uint64_t* h_res, uint32_t rw, const uint8_t* h_o, uint8_t* h_out,
-                        uint64_t* h_out_len, uint64_t* h_consumed, int32_t* h_status, uint64_t* h_unknown,
-                        uint32_t unknown_cap, uint32_t* h_nunknown, uint64_t* h_extract_hash, uint32_t extract_cap,
-                        uint32_t* h_nextract) {
-  if ((uint32_t)h_res[rw - 1]) return XCG_EOVERFLOW;   // (cache capacity: the sticky word)
-  if (h_res[5] == 2) {
-    *h_out_len = h_res[7];
-    return XCG_EOVERFLOW;
-  }
-  if (h_res[5] != 0) return XCG_ENOTSUP;
-  const uint64_t ol = h_res[0];
-  memcpy(h_out, h_o, ol);
-  *h_out_len = ol;
-  *h_consumed = h_res[1];
-  *h_status = (int32_t)(int64_t)h_res[2];
-  w->count += h_res[3];
-  const uint32_t nu = (uint32_t)h_res[4];
-  uint64_t* u = (uint64_t*)alloca(8ull * (nu ? nu : 1));
-  memcpy(u, h_res + 8, 8ull * nu);
-  std::sort(u, u + nu);
-  const uint32_t ku = nu < unknown_cap ? nu : unknown_cap;
-  if (h_unknown && ku) memcpy(h_unknown, u, 8ull * ku);
-  *h_nunknown = ku;
-  const uint32_t ne = (uint32_t)h_res[6];
-  if (ne <= extract_cap && ne <= 1024) {
-    if (ne && h_extract_hash) memcpy(h_extract_hash, h_res + 8 + 2048, 8ull * ne);
-    *h_nextract = ne;
-  }
-  return XCG_OK;
-}
-
 // One decode() in one launch with no copies: the kernel reads the input from,
 // and writes the output and results to, coherent pinned host memory, then
 // stores the call's sequence number there; the host waits on that word (a
 // launch + poll is ~11 us on this box against ~29 us for copy in, launch, copy
 // out and a stream synchronisation).  Input up to the kernel's LDS staging size.
 int decode_call_zc(xcg_ctx* c, const uint8_t* h_in, uint32_t len, uint8_t* h_out, uint64_t out_cap, uint32_t ops_cap,
-                   uint32_t rw, uint64_t* h_out_len, uint64_t* h_consumed, int32_t* h_status, uint64_t* h_unknown,
+                   uint64_t* h_out_len, uint64_t* h_consumed, int32_t* h_status, uint64_t* h_unknown,
                    uint32_t unknown_cap, uint32_t* h_nunknown, uint64_t* h_extract_hash, uint32_t extract_cap,
                    uint32_t* h_nextract) {
-  const size_t inb = align_up(len, 256), outb = align_up(out_cap ? out_cap : 1, 256), resb = align_up(8ull * rw, 256);
+  const size_t inb = align_up(len, 256), outb = align_up(out_cap ? out_cap : 1, 256), resb = align_up(8ull * xcg::SD_RES_WORDS, 256);
   const size_t need = 256 + inb + outb + resb;
   if (need > c->zc_cap) {
     if (c->zc_h) (void)hipStreamSynchronize(c->call_st);
@@ -337,7 +304,7 @@ int decode_call_zc(xcg_ctx* c, const uint8_t* h_in, uint32_t len, uint8_t* h_out
     c->zc_cap = want;
     memset(c->zc_h, 0, 256);
   }
-  const size_t scr = align_up(xcg_decode_small_scratch(ops_cap), 256);
+  const size_t scr = align_up(xcg::SD_SCRATCH_PER_OP * ops_cap, 256);
   int rc = ensure_stage(c, scr, 0);                  // (device scratch: the op lists)
   if (rc != XCG_OK) return rc;
   uint8_t* hz = c->zc_h;
@@ -381,7 +348,7 @@ int decode_call_zc(xcg_ctx* c, const uint8_t* h_in, uint32_t len, uint8_t* h_out
       }
     }
   }
-  return decode_call_results(w, h_res, rw, h_o, h_out, h_out_len, h_consumed, h_status, h_unknown, unknown_cap,
+  return decode_call_results(&w->count, h_res, h_o, h_out, h_out_len, h_consumed, h_status, h_unknown, unknown_cap,
                              h_nunknown, h_extract_hash, extract_cap, h_nextract);
 }
 }  // namespace
@@ -410,9 +377,8 @@ int xcg_decode_call(xcg_ctx* c, const uint8_t* h_in, uint32_t len, uint8_t* h_ou
     }
     if (rc != XCG_OK) return rc;
     const uint32_t ops_cap = len / 4 + 64;
-    const uint32_t rw = xcg_decode_small_res_words();
-    if (len <= xcg_decode_small_lds_in() && !dphase_on() && !getenv_flag_no_zc()) {
-      rc = decode_call_zc(c, h_in, len, h_out, out_cap, ops_cap, rw, h_out_len, h_consumed, h_status, h_unknown,
+    if (len <= xcg::SD_LDS_IN && !dphase_on() && !getenv_flag_no_zc()) {
+      rc = decode_call_zc(c, h_in, len, h_out, out_cap, ops_cap, h_out_len, h_consumed, h_status, h_unknown,
                           unknown_cap, h_nunknown, h_extract_hash, extract_cap, h_nextract);
       if (rc != XCG_ENOTSUP) return rc;
       // (fallback: the batch decoder takes it; nothing was written)
@@ -423,9 +389,9 @@ int xcg_decode_call(xcg_ctx* c, const uint8_t* h_in, uint32_t len, uint8_t* h_ou
     }
     // device: input | output | results | op lists;  host: input | output | results (one D2H brings
     // both back; the results' last word is the context's sticky word)
-    const size_t inb = align_up(len, 256), outb = align_up(out_cap ? out_cap : 1, 256), resb = align_up(8ull * rw, 256);
-    const size_t scr = align_up(xcg_decode_small_scratch(ops_cap), 256);
-    const uint32_t nph = xcg_decode_small_phases();
+    const size_t inb = align_up(len, 256), outb = align_up(out_cap ? out_cap : 1, 256), resb = align_up(8ull * xcg::SD_RES_WORDS, 256);
+    const size_t scr = align_up(xcg::SD_SCRATCH_PER_OP * ops_cap, 256);
+    const uint32_t nph = xcg::SD_PHASES;
     const size_t timb = dphase_on() ? align_up(8ull * nph, 256) : 0;
     rc = ensure_stage(c, inb + outb + resb + scr + timb, inb + outb + resb);
     if (rc != XCG_OK) return rc;
@@ -442,14 +408,14 @@ int xcg_decode_call(xcg_ctx* c, const uint8_t* h_in, uint32_t len, uint8_t* h_ou
         xcg_launch_decode_small(dm, len, &c->g, c->d_status, dm + inb + outb + resb, ops_cap, dm + inb, out_cap,
                                 w->hash, w->seg, w->count, d_res,
                                 timb ? (uint64_t*)(dm + inb + outb + resb + scr) : nullptr, nullptr, 0u, st) != 0 ||
-        hipMemcpyAsync(h_o, dm + inb, outb + 8ull * rw, hipMemcpyDeviceToHost, st) != hipSuccess)
+        hipMemcpyAsync(h_o, dm + inb, outb + 8ull * xcg::SD_RES_WORDS, hipMemcpyDeviceToHost, st) != hipSuccess)
       return XCG_EHIP;
     ctx_mark(c, st);
     if (hipStreamSynchronize(st) != hipSuccess) return XCG_EHIP;
     if (timb) {
       std::vector<uint64_t> tm(nph, 0);
       if (hipMemcpy(tm.data(), dm + inb + outb + resb + scr, 8ull * nph, hipMemcpyDeviceToHost) == hipSuccess &&
-          h_res[5] == 0) {
+          h_res[xcg::SDR_FALLBACK] == xcg::SD_FB_DONE) {
         std::lock_guard<std::mutex> g(g_dph_mu);
         g_dph_sum.resize(nph, 0.0);
         for (uint32_t k = 1; k < nph; ++k)
@@ -458,7 +424,7 @@ int xcg_decode_call(xcg_ctx* c, const uint8_t* h_in, uint32_t len, uint8_t* h_ou
         ++g_dph_calls;
       }
     }
-    const int r2 = decode_call_results(w, h_res, rw, h_o, h_out, h_out_len, h_consumed, h_status, h_unknown,
+    const int r2 = decode_call_results(&w->count, h_res, h_o, h_out, h_out_len, h_consumed, h_status, h_unknown,
                                        unknown_cap, h_nunknown, h_extract_hash, extract_cap, h_nextract);
     if (r2 != XCG_ENOTSUP) return r2;
     // (fallback: the batch decoder takes it; nothing was written)

@@ -1,16 +1,20 @@
 // The ABI layer's host-only helpers, each written once: the driver-code map,
-// the registry's UUID key, the argument predicates and the unpackers of a
-// batch's declaration / reference rows.  No HIP here, so the whole file runs
+// the registry's UUID key, the argument predicates, the unpackers of a
+// batch's declaration / reference rows and of the per-call decoder's result
+// words.  No HIP here, so the whole file runs
 // under sanitizers on the CPU (oracle/api_host_harness.cc).
 #pragma once
+#include <alloca.h>
 #include <ctype.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <algorithm>
 #include <string>
 #include <vector>
 
 #include "../../include/xcgpu.h"
+#include "xcg_decode_words.h"
 #include "xcg_rc.h"
 
 // A driver's return code (0 or an XCG_RC_* value) as an ABI status; anything
@@ -102,4 +106,39 @@ static inline uint32_t unpack_ref_rows(const uint32_t* rows, uint32_t n, uint32_
     if (h_ref) h_ref[j] = e[3] & ROW_REF_MASK;
   }
   return n;
+}
+
+// The result words of one decode_small_kernel launch (xcg_decode_words.h) ->
+// the call's outputs.  XCG_ENOTSUP: the kernel declined (fallback); nothing
+// was written.  *win_count: the window's declare count, advanced.
+static inline int decode_call_results(uint64_t* win_count, const uint64_t* h_res, const uint8_t* h_o, uint8_t* h_out,
+                                      uint64_t* h_out_len, uint64_t* h_consumed, int32_t* h_status,
+                                      uint64_t* h_unknown, uint32_t unknown_cap, uint32_t* h_nunknown,
+                                      uint64_t* h_extract_hash, uint32_t extract_cap, uint32_t* h_nextract) {
+  using namespace xcg;
+  if ((uint32_t)h_res[SD_RES_STICKY]) return XCG_EOVERFLOW;   // (cache capacity: the sticky word)
+  if (h_res[SDR_FALLBACK] == SD_FB_ROOM) {
+    *h_out_len = h_res[SDR_NEED];
+    return XCG_EOVERFLOW;
+  }
+  if (h_res[SDR_FALLBACK] != SD_FB_DONE) return XCG_ENOTSUP;
+  const uint64_t ol = h_res[SDR_OUT_LEN];
+  if (ol) memcpy(h_out, h_o, ol);
+  *h_out_len = ol;
+  *h_consumed = h_res[SDR_CONSUMED];
+  *h_status = (int32_t)(int64_t)h_res[SDR_STATUS];
+  *win_count += h_res[SDR_DECLARES];
+  const uint32_t nu = (uint32_t)h_res[SDR_UNKNOWNS];
+  uint64_t* u = (uint64_t*)alloca(8ull * (nu ? nu : 1));
+  memcpy(u, h_res + SD_RES_UNKNOWN, 8ull * nu);
+  std::sort(u, u + nu);
+  const uint32_t ku = nu < unknown_cap ? nu : unknown_cap;
+  if (h_unknown && ku) memcpy(h_unknown, u, 8ull * ku);
+  *h_nunknown = ku;
+  const uint32_t ne = (uint32_t)h_res[SDR_EXTRACTS];
+  if (ne <= extract_cap && ne <= SD_EMAX) {
+    if (ne && h_extract_hash) memcpy(h_extract_hash, h_res + SD_RES_EXTRACT, 8ull * ne);
+    *h_nextract = ne;
+  }
+  return XCG_OK;
 }

@@ -1,7 +1,7 @@
 // The library's internal interface: every struct and every extern "C" function
 // that crosses translation units inside libxcgpu (the host ABI layer
 // xcg_ctx.hip and xcg_api_*.hip, xcg_pipe.cpp and the kernel drivers
-// xcg_encode_* / xcg_decode / xcg_lru / xcg_pair / xcg_hash).  The file that defines one of these functions
+// xcg_encode_* / xcg_decode* / xcg_cache_* / xcg_lru / xcg_pair / xcg_hash).  The file that defines one of these functions
 // and every file that calls it include this header, so a prototype that drifts
 // is a compile error.  Plain data only: xcg_pipe.cpp compiles it as host C++.
 //
@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "xcg_decode_words.h"   // the decode scratch words by name
 #include "xcg_devmem.h"
 #include "xcg_rc.h"      // the drivers' return codes (XCG_RC_*)
 
@@ -257,10 +258,10 @@ struct XcgDecodeScratch {
   uint64_t* u_keys = nullptr;      // unknown-hash set, 2 * unknown_cap slots
   uint64_t* unknown = nullptr;
   uint64_t* unknown_pos = nullptr;
-  uint32_t* nunknown = nullptr;    // 4 words: [0] unknown hashes, [1] hashes whose EXTRACTs differ, [2] their occurrences
-  uint64_t* scratch = nullptr;     // [0] total out, [1] REF block, [2] BACKREF error, [3] duplicate EXTRACTs - 1, [4] declares,
-                                   // [5] BACKREFs, [6] t_end
-  uint64_t* h_scratch = nullptr;   // pinned copy of scratch[0..5], [6] nunknown | flagged hashes << 32, [12..14] reuse stats
+  // the batch's counters and single words, and where they come back on the host (pinned): xcg_decode_words.h
+  xcg::DecCounts* counts = nullptr;
+  xcg::DecScratch* scratch = nullptr;
+  xcg::DecHostWords* h_scratch = nullptr;
   uint32_t chunk_cap = 0;
   uint64_t* chunk_tmp = nullptr;   // 4 * n u64: n_decl, n_bref, decl_base, n_decl_emit
   uint4* d_tail = nullptr;         // 256 declare records (window update)
@@ -385,6 +386,9 @@ struct XcgBulkLearn {
 extern "C" int xcg_bulk_learn(const XcgBulkLearn* a, hipStream_t st);
 extern "C" int xcg_bulk_export(const XcgCacheView* g, const XcgLruState* lru, uint32_t live, uint8_t* d_segs,
                                uint64_t* d_hash, hipStream_t st);
+// (xcg_decode.hip) exclusive scan of n u64 lengths into off[], their sum into *total: one workgroup
+extern "C" void xcg_launch_exclusive_scan(const uint64_t* len, uint64_t* off, uint32_t n, uint64_t* total,
+                                          hipStream_t stream);
 extern "C" int xcg_launch_pack(const uint8_t* src, const uint64_t* src_off, const uint64_t* len, uint32_t n,
                                uint8_t* dst, uint64_t* dst_off, uint64_t* d_total, hipStream_t stream);
 extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, uint64_t* block_pos_out,
@@ -394,10 +398,6 @@ extern "C" int xcg_launch_decode_small(const uint8_t* in, uint32_t len, const Xc
                                        void* scratch, uint32_t ops_cap, uint8_t* out, uint64_t out_cap,
                                        uint64_t* win_hash, uint8_t* win_seg, uint64_t win_count, uint64_t* res,
                                        uint64_t* tim, uint32_t* flag, uint32_t seq, hipStream_t stream);
-extern "C" uint64_t xcg_decode_small_scratch(uint32_t ops_cap);
-extern "C" uint32_t xcg_decode_small_res_words(void);
-extern "C" uint32_t xcg_decode_small_phases(void);
-extern "C" uint32_t xcg_decode_small_lds_in(void);
 
 // (xcg_ctx.hip for xcg_pipe.cpp) a connecting pipe takes and drops its registry context
 // (connect_hold: xcg_ctx_connect with the hold taken under the registry lock)

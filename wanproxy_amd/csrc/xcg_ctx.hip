@@ -305,8 +305,8 @@ int ensure_dscratch(xcg_ctx* c, uint64_t max_extracts) {
         m.dev(&d.unknown, 8ull * UNKNOWN_CAP) && m.dev(&d.u_keys, 16ull * UNKNOWN_CAP) &&
         m.dev(&d.x_owner, 8ull * cap) && m.dev(&d.x_flag, 4ull * cap) &&
         m.dev(&d.dup_slot, 4ull * (cap / 2)) && m.dev(&d.dup_pos, 8ull * (cap / 2)) &&
-        m.dev(&d.unknown_pos, 8ull * UNKNOWN_CAP) && m.dev(&d.nunknown, 16) &&
-        m.dev(&d.scratch, 64) && m.pinned(&d.h_scratch, 128))) {
+        m.dev(&d.unknown_pos, 8ull * UNKNOWN_CAP) && m.dev(&d.counts, sizeof(*d.counts)) &&
+        m.dev(&d.scratch, sizeof(*d.scratch)) && m.pinned(&d.h_scratch, sizeof(*d.h_scratch)))) {
     free_dscratch(c);
     return XCG_ENOMEM;
   }

@@ -1,5 +1,6 @@
 // Wave-level pieces of the XCodec op walk shared by the decode kernels
-// (xcg_decode.hip: one stream per batch; xcg_decode_indep.hip: one fresh
+// (xcg_decode.hip, xcg_decode_bounded.hip and xcg_decode_small.hip through
+// xcg_decode_batch.h: one stream per batch or call; xcg_decode_indep.hip: one fresh
 // decoder per chunk; xcg_decode_group.hip: one per group of chunks): the op
 // search, the literal-run copy, the EXTRACT payload hash, the 2 KiB segment
 // copy, and the per-wave LDS decoder (cache table and window) of the

@@ -28,8 +28,8 @@
 // the sequential one (by induction over stream time: every lookup result then
 // equals the LRU state the sequential encoder has at that point); otherwise
 // the chunks with an inconsistent lookup are parsed again with the new times.
-// (The decoder's references follow from the stream, so xcg_decode.hip only
-// alternates classification and these times; see dec_classify_kernel.)
+// (The decoder's references follow from the stream, so xcg_decode_bounded.hip
+// only alternates classification and these times; see dec_classify_kernel.)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
