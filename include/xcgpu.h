@@ -20,6 +20,10 @@
  *                                                      xcodec/xcodec_encoder.cc:74-274
  *       (one encode() call per chunk, exactly as tack / XCodecPipePair issue
  *        them: programs/tack/tack.cc:308-321, xcodec/xcodec_pipe_pair.cc:596-630)
+ *   xcg_encode_refmap_batch / xcg_encode_host_refmap
+ *       the same call's third parameter: every hash it REF'd and where the
+ *       segment lies in its input          xcodec/xcodec_encoder.cc:364-371,
+ *                                          xcodec/xcodec_pipe_pair.cc:239-268,610-618
  *   xcg_decode_batch / xcg_decode_host / xcg_window_*
  *       bool XCodecDecoder::decode(Buffer *output, Buffer *input,
  *                                  std::set<uint64_t>& unknown_hashes)
@@ -323,6 +327,62 @@ int xcg_encode_batch(xcg_ctx *ctx, int semantics, const uint8_t *d_in, const uin
 int xcg_encode_host(xcg_ctx *ctx, int semantics, const uint8_t *h_in, uint64_t in_len,
                     const uint64_t *h_chunk_off, const uint32_t *h_chunk_len, uint32_t n, uint8_t *h_out,
                     uint64_t out_cap, const uint64_t *h_out_off, uint64_t *h_out_len);
+
+/*
+ * The third parameter of XCodecEncoder::encode(output, input, refmap)
+ * (xcodec/xcodec_encoder.h:42): the map from every hash the call REF'd to its
+ * segment, which XCodecPipePair keeps per unacknowledged frame to answer <ASK>
+ * with <LEARN> (xcodec/xcodec_pipe_pair.cc:239-268, 610-618).  It is a function
+ * of the call's output bytes: chunk i's encoding d_enc[d_enc_off[i] ..
+ * + d_enc_len[i]) (any alignment; the d_out / d_out_off / d_out_len just given
+ * to xcg_encode_batch) is walked op by op, tracking the input position -- a
+ * literal byte or an ESCAPE pair is one input byte, EXTRACT and REF 2048 -- and
+ * every REF gives (hash, input position): find_reference only emits a REF on
+ * byte equality (xcodec_encoder.cc:382-390), so the segment IS the chunk's
+ * input at that position.  Per chunk the first occurrence of each hash is kept
+ * (refmap->find(hash) == end(), :364-371) and the entries are ordered by
+ * ascending unsigned hash, std::map's iteration order.  Entry k of chunk i goes
+ * to d_ref_hash[i * ref_cap + k] (host byte order) and d_ref_pos[i * ref_cap + k]
+ * (relative to the chunk's input); d_ref_count[i] is the full number of entries
+ * (<= XCG_REFMAP_MAX, what 512 KiB of input can reference), of which only the
+ * first ref_cap, in hash order, are written -- entries past the count are not
+ * touched.  d_ref_walked[i] (nullable array) is the number of encoded bytes the
+ * walk covered: d_enc_len[i] for a whole encoder output.  The walk ends at the
+ * first thing no encoder writes -- a lone trailing F1, an op cut by the chunk's
+ * end, an opcode other than ESCAPE / EXTRACT / REF (the encoder never emits
+ * BACKREF, :343-372), the REF that would make entry XCG_REFMAP_MAX + 1 -- and
+ * what was found before it stands; no byte outside the chunk is read.
+ * Asynchronous on `stream`, ordered behind the context's earlier work; no
+ * allocation, no readback.  n == 0 is XCG_OK.  max_enc_len bounds every
+ * d_enc_len[i] and is at most xcg_encode_bound(512 KiB) (XCG_EINVAL beyond; so
+ * are null pointers other than d_ref_walked); a longer chunk gets count 0,
+ * walked 0 and bit 3 of the context's status word.
+ *   In-band contexts: a pure function of the bytes, whichever semantics made
+ *   them; first_chunk is ignored.
+ *   XCG_FLAG_NULLCACHE: every count is 0 (lookups always miss, so every F1 02
+ *   is a declaration); d_ref_walked is still filled.
+ *   XCG_FLAG_OOB: an out-of-band declaration is written as F1 02 BE64 too, and
+ *   encode_declaration passes no refmap (:288-295).  Chunk i is chunk
+ *   first_chunk + i of the context's last XCG_SEM_STREAM batch, and a REF whose
+ *   (position, hash) is one of that chunk's declarations (xcg_last_declarations)
+ *   is no entry.  XCG_ENOTSUP, with nothing written, when those rows are not
+ *   there: the context's last encode batch was not a stream batch, or on a
+ *   bounded context the chunks precede the batch's last sub-batch (as
+ *   xcg_last_declarations); XCG_EINVAL when first_chunk + n exceeds the batch.
+ * xcg_encode_host_refmap is xcg_encode_host with the refmap outputs added
+ * (host arrays of the same shapes, all non-null): the call above runs on the
+ * context's staging before the outputs are copied back, and the entries come
+ * back in the same synchronisation as the lengths.
+ */
+#define XCG_REFMAP_MAX 256u
+int xcg_encode_refmap_batch(xcg_ctx *ctx, const uint8_t *d_enc, const uint64_t *d_enc_off,
+                            const uint64_t *d_enc_len, uint32_t n, uint32_t max_enc_len, uint32_t first_chunk,
+                            uint64_t *d_ref_hash, uint32_t *d_ref_pos, uint32_t ref_cap,
+                            uint32_t *d_ref_count, uint64_t *d_ref_walked /* nullable */, void *stream);
+int xcg_encode_host_refmap(xcg_ctx *ctx, int semantics, const uint8_t *h_in, uint64_t in_len,
+                           const uint64_t *h_chunk_off, const uint32_t *h_chunk_len, uint32_t n, uint8_t *h_out,
+                           uint64_t out_cap, const uint64_t *h_out_off, uint64_t *h_out_len,
+                           uint64_t *h_ref_hash, uint32_t *h_ref_pos, uint32_t ref_cap, uint32_t *h_ref_count);
 
 /* *h_nref of xcg_encode_call on a cache whose lookups change nothing (an
  * unbounded memory cache, the null cache): no reference list is kept. */

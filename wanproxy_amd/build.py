@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # (the encoder's units first: the two stream units are the longest compiles)
 SRCS = ['csrc/xcg_encode_stream.hip', 'csrc/xcg_encode_stream_lru.hip', 'csrc/xcg_encode_indep.hip',
         'csrc/xcg_encode_group.hip', 'csrc/xcg_encode_screen.hip', 'csrc/xcg_ctx.hip', 'csrc/xcg_api_cache.hip',
-        'csrc/xcg_api_encode.hip', 'csrc/xcg_api_decode.hip', 'csrc/xcg_decode.hip',
+        'csrc/xcg_encode_refmap.hip', 'csrc/xcg_api_encode.hip', 'csrc/xcg_api_decode.hip', 'csrc/xcg_decode.hip',
         'csrc/xcg_decode_bounded.hip', 'csrc/xcg_decode_small.hip',
         'csrc/xcg_decode_indep.hip', 'csrc/xcg_decode_group.hip', 'csrc/xcg_hash.hip', 'csrc/xcg_lru.hip',
         'csrc/xcg_pair.hip', 'csrc/xcg_cache_bulk.hip', 'csrc/xcg_cache_point.hip', 'csrc/xcg_pipe.cpp', 'csrc/xcg_deflate.hip', 'csrc/xcg_inflate.hip',

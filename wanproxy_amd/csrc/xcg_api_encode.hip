@@ -53,6 +53,7 @@ int encode_batch_impl(xcg_ctx* c, int semantics, const uint8_t* d_in, const uint
   if (max_chunk_len > (1u << 19)) return XCG_EINVAL;
   DeviceGuard g(c->device);
   ctx_order(c, (hipStream_t)stream);
+  c->last_stream_n = 0;              // (set again below once a stream batch has left its rows)
   // A null cache has no state to carry: both semantics are the same pass.
   if (semantics == XCG_SEM_STREAM && !(c->flags & XCG_FLAG_NULLCACHE)) {
     // declaration slots per chunk: a chunk of L bytes declares at most L / 2048
@@ -74,6 +75,7 @@ int encode_batch_impl(xcg_ctx* c, int semantics, const uint8_t* d_in, const uint
       if (decls != ~0u) c->seed_next = decls > 0;
     }
     c->last_rounds = rounds;
+    if (rc == 0) c->last_stream_n = n;
     return status_of(rc);   // (0, XCG_RC_HIP, _OVERFLOW, and from the bounded and pair drivers _NOTSUP)
   }
   // A fresh bounded cache per chunk evicts nothing while the chunk's
@@ -82,6 +84,92 @@ int encode_batch_impl(xcg_ctx* c, int semantics, const uint8_t* d_in, const uint
   int rc = xcg_launch_encode_independent(d_in, d_chunk_off, d_chunk_len, n, max_chunk_len, c->flags, d_out,
                                          d_out_off, d_out_len, d_stats, c->d_status, (hipStream_t)stream);
   return status_of(rc);   // (0, XCG_RC_INVAL or XCG_RC_HIP)
+}
+
+// xcg_encode_host, and with `rm` xcg_encode_host_refmap: the same call with the
+// refmap launch behind the batch, its rows beside the lengths.
+struct HostRefmap {
+  uint64_t* hash;
+  uint32_t* pos;
+  uint32_t cap;
+  uint32_t* count;
+};
+
+int encode_host_impl(xcg_ctx* c, int semantics, const uint8_t* h_in, uint64_t in_len, const uint64_t* h_chunk_off,
+                     const uint32_t* h_chunk_len, uint32_t n, uint8_t* h_out, uint64_t out_cap,
+                     const uint64_t* h_out_off, uint64_t* h_out_len, const HostRefmap* rm) {
+  if (!c || (n && (!h_in || !h_chunk_off || !h_chunk_len || !h_out || !h_out_off || !h_out_len))) return XCG_EINVAL;
+  if (n == 0) return XCG_OK;
+  uint32_t maxlen = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (h_chunk_off[i] + h_chunk_len[i] > in_len) return XCG_EINVAL;
+    if (h_out_off[i] + xcg_encode_bound(h_chunk_len[i]) > out_cap) return XCG_EINVAL;
+    if (h_chunk_len[i] > maxlen) maxlen = h_chunk_len[i];
+  }
+  DeviceGuard g(c->device);
+  // staging (kept by the context): [off n][oo n][ol n][len n] | input | output slots
+  //                                | (refmap) [count n][hash n * cap][pos n * cap]
+  const size_t meta = align_up(28ull * n, 256), inb = align_up(in_len ? in_len : 1, 256),
+               outb = align_up(out_cap ? out_cap : 1, 256);
+  const uint64_t rows = rm ? (uint64_t)n * rm->cap : 0;
+  const size_t rcnt = rm ? align_up(4ull * n, 256) : 0, rhash = rm ? align_up(8ull * rows + 1, 256) : 0,
+               rpos = rm ? align_up(4ull * rows + 1, 256) : 0;
+  const size_t refb = rcnt + rhash + rpos;
+  int rc = ensure_stage(c, meta + inb + outb + refb, meta + inb + outb + refb);
+  if (rc != XCG_OK) return rc;
+  uint8_t* hm = c->stage_h;
+  uint8_t* dm = c->stage_d;
+  memcpy(hm, h_chunk_off, 8ull * n);
+  memcpy(hm + 8ull * n, h_out_off, 8ull * n);
+  memcpy(hm + 24ull * n, h_chunk_len, 4ull * n);
+  memcpy(hm + meta, h_in, in_len);
+  const hipStream_t st = c->call_st;
+  const uint64_t* d_off = (const uint64_t*)dm;
+  const uint64_t* d_oo = (const uint64_t*)(dm + 8ull * n);
+  uint64_t* d_ol = (uint64_t*)(dm + 16ull * n);
+  const uint32_t* d_len = (const uint32_t*)(dm + 24ull * n);
+  uint8_t* d_out = dm + meta + inb;
+  const size_t ref0 = meta + inb + outb;
+  if (hipMemcpyAsync(dm, hm, meta + in_len, hipMemcpyHostToDevice, st) != hipSuccess) return XCG_EHIP;
+  rc = xcg_encode_batch(c, semantics, dm + meta, d_off, d_len, n, maxlen, d_out, d_oo, d_ol, nullptr, st);
+  if (rc != XCG_OK) return rc;
+  if (rm) {
+    rc = xcg_encode_refmap_batch(c, d_out, d_oo, d_ol, n, (uint32_t)xcg_encode_bound(maxlen), 0,
+                                 (uint64_t*)(dm + ref0 + rcnt), (uint32_t*)(dm + ref0 + rcnt + rhash), rm->cap,
+                                 (uint32_t*)(dm + ref0), nullptr, st);
+    if (rc != XCG_OK) return rc;
+  }
+  uint64_t* ol = (uint64_t*)(hm + 16ull * n);
+  if (hipMemcpyAsync(ol, d_ol, 8ull * n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(c->h_status, c->d_status, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      (rm && hipMemcpyAsync(hm + ref0, dm + ref0, rcnt + rhash + 4ull * rows, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+      hipStreamSynchronize(st) != hipSuccess)
+    return XCG_EHIP;
+  if (*c->h_status) return XCG_EOVERFLOW;
+  // only the bytes each slot holds come back
+  uint8_t* ho = hm + meta + inb;
+  for (uint32_t i = 0; i < n; ++i) {
+    h_out_len[i] = ol[i];
+    if (ol[i] && hipMemcpyAsync(ho + h_out_off[i], d_out + h_out_off[i], ol[i], hipMemcpyDeviceToHost, st) != hipSuccess)
+      return XCG_EHIP;
+  }
+  if (rm) {                                          // (entries past a chunk's count stay as the caller left them)
+    const uint32_t* cnt = (const uint32_t*)(hm + ref0);
+    const uint64_t* hh = (const uint64_t*)(hm + ref0 + rcnt);
+    const uint32_t* hp = (const uint32_t*)(hm + ref0 + rcnt + rhash);
+    for (uint32_t i = 0; i < n; ++i) {
+      rm->count[i] = cnt[i];
+      const uint32_t k = cnt[i] < rm->cap ? cnt[i] : rm->cap;
+      if (k) {
+        memcpy(rm->hash + (uint64_t)i * rm->cap, hh + (uint64_t)i * rm->cap, 8ull * k);
+        memcpy(rm->pos + (uint64_t)i * rm->cap, hp + (uint64_t)i * rm->cap, 4ull * k);
+      }
+    }
+  }
+  if (hipStreamSynchronize(st) != hipSuccess) return XCG_EHIP;
+  for (uint32_t i = 0; i < n; ++i)
+    if (ol[i]) memcpy(h_out + h_out_off[i], ho + h_out_off[i], ol[i]);
+  return XCG_OK;
 }
 }  // namespace
 
@@ -108,52 +196,53 @@ int xcg_encode_batch(xcg_ctx* c, int semantics, const uint8_t* d_in, const uint6
 int xcg_encode_host(xcg_ctx* c, int semantics, const uint8_t* h_in, uint64_t in_len, const uint64_t* h_chunk_off,
                     const uint32_t* h_chunk_len, uint32_t n, uint8_t* h_out, uint64_t out_cap,
                     const uint64_t* h_out_off, uint64_t* h_out_len) {
-  if (!c || (n && (!h_in || !h_chunk_off || !h_chunk_len || !h_out || !h_out_off || !h_out_len))) return XCG_EINVAL;
+  return encode_host_impl(c, semantics, h_in, in_len, h_chunk_off, h_chunk_len, n, h_out, out_cap, h_out_off,
+                          h_out_len, nullptr);
+}
+
+int xcg_encode_host_refmap(xcg_ctx* c, int semantics, const uint8_t* h_in, uint64_t in_len,
+                           const uint64_t* h_chunk_off, const uint32_t* h_chunk_len, uint32_t n, uint8_t* h_out,
+                           uint64_t out_cap, const uint64_t* h_out_off, uint64_t* h_out_len, uint64_t* h_ref_hash,
+                           uint32_t* h_ref_pos, uint32_t ref_cap, uint32_t* h_ref_count) {
+  if (!h_ref_hash || !h_ref_pos || !h_ref_count) return XCG_EINVAL;
+  const HostRefmap rm{h_ref_hash, h_ref_pos, ref_cap, h_ref_count};
+  return encode_host_impl(c, semantics, h_in, in_len, h_chunk_off, h_chunk_len, n, h_out, out_cap, h_out_off,
+                          h_out_len, &rm);
+}
+
+int xcg_encode_refmap_batch(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_enc_off, const uint64_t* d_enc_len,
+                            uint32_t n, uint32_t max_enc_len, uint32_t first_chunk, uint64_t* d_ref_hash,
+                            uint32_t* d_ref_pos, uint32_t ref_cap, uint32_t* d_ref_count, uint64_t* d_ref_walked,
+                            void* stream) {
+  if (!c) return XCG_EINVAL;
   if (n == 0) return XCG_OK;
-  uint32_t maxlen = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (h_chunk_off[i] + h_chunk_len[i] > in_len) return XCG_EINVAL;
-    if (h_out_off[i] + xcg_encode_bound(h_chunk_len[i]) > out_cap) return XCG_EINVAL;
-    if (h_chunk_len[i] > maxlen) maxlen = h_chunk_len[i];
+  if (!d_enc || !d_enc_off || !d_enc_len || !d_ref_hash || !d_ref_pos || !d_ref_count) return XCG_EINVAL;
+  if (max_enc_len > xcg_encode_bound(1u << 19)) return XCG_EINVAL;
+  XcgRefmapArgs a{};
+  a.enc = d_enc; a.enc_off = d_enc_off; a.enc_len = d_enc_len; a.n = n;
+  a.max_len = max_enc_len;
+  a.collect = (c->flags & XCG_FLAG_NULLCACHE) ? 0 : 1;
+  if (a.collect && (c->flags & XCG_FLAG_OOB)) {
+    // the declaration rows of the chunks [first_chunk, first_chunk + n) of the last stream batch
+    if (!c->last_stream_n || !c->bs.decl || !c->bs.ndecl) return XCG_ENOTSUP;
+    uint32_t base = 0;                                 // (bounded: rows of the last sub-batch only)
+    if (c->bounded || c->pair) base = c->pair ? xcg_pair_state_last_base(c->pair) : c->lru.last_base;
+    if (first_chunk < base) return XCG_ENOTSUP;
+    if ((uint64_t)first_chunk + n > c->last_stream_n) return XCG_EINVAL;
+    const uint32_t row0 = first_chunk - base;
+    a.maxd = c->bs.last_maxd;
+    a.decl = (const uint8_t*)c->bs.decl + 16ull * row0 * a.maxd;
+    a.ndecl = c->bs.ndecl + row0;
   }
+  a.ref_hash = d_ref_hash; a.ref_pos = d_ref_pos; a.ref_cap = ref_cap;
+  a.ref_count = d_ref_count;
+  a.walked = d_ref_walked;
+  a.status = c->d_status;
   DeviceGuard g(c->device);
-  // staging (kept by the context): [off n][oo n][ol n][len n] | input | output slots
-  const size_t meta = align_up(28ull * n, 256), inb = align_up(in_len ? in_len : 1, 256),
-               outb = align_up(out_cap ? out_cap : 1, 256);
-  int rc = ensure_stage(c, meta + inb + outb, meta + inb + outb);
-  if (rc != XCG_OK) return rc;
-  uint8_t* hm = c->stage_h;
-  uint8_t* dm = c->stage_d;
-  memcpy(hm, h_chunk_off, 8ull * n);
-  memcpy(hm + 8ull * n, h_out_off, 8ull * n);
-  memcpy(hm + 24ull * n, h_chunk_len, 4ull * n);
-  memcpy(hm + meta, h_in, in_len);
-  const hipStream_t st = c->call_st;
-  const uint64_t* d_off = (const uint64_t*)dm;
-  const uint64_t* d_oo = (const uint64_t*)(dm + 8ull * n);
-  uint64_t* d_ol = (uint64_t*)(dm + 16ull * n);
-  const uint32_t* d_len = (const uint32_t*)(dm + 24ull * n);
-  uint8_t* d_out = dm + meta + inb;
-  if (hipMemcpyAsync(dm, hm, meta + in_len, hipMemcpyHostToDevice, st) != hipSuccess) return XCG_EHIP;
-  rc = xcg_encode_batch(c, semantics, dm + meta, d_off, d_len, n, maxlen, d_out, d_oo, d_ol, nullptr, st);
-  if (rc != XCG_OK) return rc;
-  uint64_t* ol = (uint64_t*)(hm + 16ull * n);
-  if (hipMemcpyAsync(ol, d_ol, 8ull * n, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipMemcpyAsync(c->h_status, c->d_status, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess)
-    return XCG_EHIP;
-  if (*c->h_status) return XCG_EOVERFLOW;
-  // only the bytes each slot holds come back
-  uint8_t* ho = hm + meta + inb;
-  for (uint32_t i = 0; i < n; ++i) {
-    h_out_len[i] = ol[i];
-    if (ol[i] && hipMemcpyAsync(ho + h_out_off[i], d_out + h_out_off[i], ol[i], hipMemcpyDeviceToHost, st) != hipSuccess)
-      return XCG_EHIP;
-  }
-  if (hipStreamSynchronize(st) != hipSuccess) return XCG_EHIP;
-  for (uint32_t i = 0; i < n; ++i)
-    if (ol[i]) memcpy(h_out + h_out_off[i], ho + h_out_off[i], ol[i]);
-  return XCG_OK;
+  ctx_order(c, (hipStream_t)stream);
+  const int rc = xcg_launch_encode_refmap(&a, (hipStream_t)stream);
+  ctx_mark(c, (hipStream_t)stream);
+  return status_of(rc);   // (0, XCG_RC_INVAL or XCG_RC_HIP)
 }
 
 int xcg_encode_call(xcg_ctx* c, const uint8_t* h_in, uint32_t len, uint8_t* h_out, uint64_t out_cap,
@@ -246,6 +335,7 @@ int xcg_encode_batch_grouped(xcg_ctx* c, const uint8_t* d_in, const uint64_t* d_
   if (!ctx_fresh_cache_fits(c, group_declarations(max_group_len))) return XCG_ENOTSUP;
   DeviceGuard g(c->device);
   ctx_order(c, (hipStream_t)stream);
+  c->last_stream_n = 0;              // (the last encode batch is no stream batch now)
   const int rc = xcg_launch_encode_group(d_in, d_chunk_off, d_chunk_len, n, d_group_first, n_groups, max_group_len,
                                          c->flags, d_out, d_out_off, d_out_len, d_stats, c->d_status,
                                          (hipStream_t)stream);

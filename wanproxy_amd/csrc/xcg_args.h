@@ -333,6 +333,28 @@ struct XcgGroupDecodeArgs {
   int32_t* status;
 };
 
+// Arguments of the encoder refmap driver (xcg_launch_encode_refmap): per chunk
+// its encoder output and the caller's entry rows; of a context its sticky
+// status word and, out of band, the declaration rows of its last stream batch.
+struct XcgRefmapArgs {
+  const uint8_t* enc;
+  const uint64_t* enc_off;
+  const uint64_t* enc_len;
+  uint32_t n;
+  uint32_t max_len;         // the caller's bound on every encoded length
+  int collect;              // 0: no REF is an entry (null cache); the walk alone
+  const void* decl;         // (out of band) uint4 rows (lo, hi, pos, -) of chunk i at decl[i * maxd ..); null: none
+  const uint32_t* ndecl;    // [n]
+  uint32_t maxd;
+  uint64_t* ref_hash;       // [n * ref_cap]
+  uint32_t* ref_pos;        // [n * ref_cap]
+  uint32_t ref_cap;
+  uint32_t* ref_count;      // [n]
+  uint64_t* walked;         // nullable [n]
+  int32_t* status;
+};
+extern "C" int xcg_launch_encode_refmap(const XcgRefmapArgs* a, hipStream_t stream);
+
 extern "C" int xcg_launch_encode_stream(const XcgStreamArgs* a, int* rounds_out, hipStream_t stream);
 extern "C" int xcg_lru_encode_stream(const XcgStreamArgs* a, XcgLruState* L, int* rounds_out, hipStream_t st);
 extern "C" int xcg_lru_times(const LruBatch* b, XcgLruState* L, hipStream_t st);

@@ -44,6 +44,7 @@ struct xcg_ctx {
   GpuCache g;
   BatchScratch bs;
   int last_rounds = 0;
+  uint32_t last_stream_n = 0;      // chunks of the last encode batch if it was a stream batch with rows in bs, else 0
   DecodeScratch ds;
   xcg_window* own_win = nullptr;   // default window (lazily allocated)
   xcg_window* cur_win = nullptr;   // window used by decodes (own_win unless set)

@@ -28,7 +28,8 @@ XCG_FLAG_NULLCACHE = 0x2
 XCG_SEM_INDEPENDENT = 0
 XCG_SEM_STREAM = 1
 XCG_EOVERFLOW = -75
-XCG_CHUNK_NOROOM = 4    # per-chunk status of xcg_decode_batch_independent: the output slot is too small
+XCG_REFMAP_MAX = 256    # entries of one encode() call's refmap (what 512 KiB of input can reference)
+XCG_CHUNK_NOROOM = 4   # per-chunk status of xcg_decode_batch_independent: the output slot is too small
 
 _lib = None
 
@@ -126,6 +127,13 @@ def lib():
     L.xcg_encode_batch.restype = C.c_int
     L.xcg_encode_host.argtypes = [vp, C.c_int, u8p, C.c_uint64, u64p, u32p, C.c_uint32, u8p, C.c_uint64, u64p, u64p]
     L.xcg_encode_host.restype = C.c_int
+    if hasattr(L, 'xcg_encode_refmap_batch'):   # (an XCGPU_LIB build from before the refmap: calling them raises)
+        L.xcg_encode_refmap_batch.argtypes = [vp, u8p, u64p, u64p, C.c_uint32, C.c_uint32, C.c_uint32, u64p, u32p,
+                                              C.c_uint32, u32p, u64p, vp]
+        L.xcg_encode_refmap_batch.restype = C.c_int
+        L.xcg_encode_host_refmap.argtypes = [vp, C.c_int, u8p, C.c_uint64, u64p, u32p, C.c_uint32, u8p, C.c_uint64,
+                                             u64p, u64p, u64p, u32p, C.c_uint32, u32p]
+        L.xcg_encode_host_refmap.restype = C.c_int
     L.xcg_decode_batch.argtypes = [vp, u8p, u64p, u32p, C.c_uint32, C.c_uint32, u8p, C.c_uint64, u64p, u64p, vp, u64p,
                                    u64p, C.c_uint32, vp, u64p, vp]
     L.xcg_decode_batch.restype = C.c_int
@@ -474,6 +482,51 @@ class Context:
             return res, d_st.cpu().numpy().view(np.uint32).reshape(n, 4)
         return res
 
+    def encode_refmap_device(self, d_enc, d_enc_off, d_enc_len, n, max_enc_len, d_ref_hash, d_ref_pos, ref_cap,
+                             d_ref_count, d_ref_walked=None, first_chunk=0, stream=None):
+        """Raw launch of xcg_encode_refmap_batch on device tensors: the refmap
+        rows of the encoder outputs d_enc / d_enc_off / d_enc_len (what
+        encode_batch_device just wrote); asynchronous on `stream`."""
+        _check(lib().xcg_encode_refmap_batch(
+            self.h, C.c_void_p(d_enc.data_ptr()), C.c_void_p(d_enc_off.data_ptr()), C.c_void_p(d_enc_len.data_ptr()),
+            int(n), int(max_enc_len), int(first_chunk), C.c_void_p(d_ref_hash.data_ptr()),
+            C.c_void_p(d_ref_pos.data_ptr()), int(ref_cap), C.c_void_p(d_ref_count.data_ptr()),
+            C.c_void_p(d_ref_walked.data_ptr()) if d_ref_walked is not None else None, _stream_ptr(stream)))
+
+    def encode_chunks_refmap(self, data, offs, lens, semantics=XCG_SEM_STREAM):
+        """encode_chunks with each call's refmap (xcg_encode_host_refmap), the
+        third parameter of XCodecEncoder::encode: returns (encs, refmaps), one
+        ordered {hash: segment bytes} per chunk, ascending by hash as std::map
+        iterates, the segments cut from `data` at the reported positions."""
+        a = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        n = int(offs.size)
+        if n == 0:
+            return [], []
+        bounds = 2 * lens.astype(np.uint64) + 16
+        oo = np.zeros(n, dtype=np.uint64)
+        oo[1:] = np.cumsum(bounds)[:-1]
+        out = np.zeros(int(bounds.sum()), dtype=np.uint8)
+        ol = np.zeros(n, dtype=np.uint64)
+        cap = XCG_REFMAP_MAX
+        rh = np.zeros(n * cap, dtype=np.uint64)
+        rp = np.zeros(n * cap, dtype=np.uint32)
+        rn = np.zeros(n, dtype=np.uint32)
+        src = a if a.size else np.zeros(1, np.uint8)
+        _check(lib().xcg_encode_host_refmap(self.h, semantics, src.ctypes.data, a.size, offs.ctypes.data,
+                                            lens.ctypes.data, n, out.ctypes.data, out.size, oo.ctypes.data,
+                                            ol.ctypes.data, rh.ctypes.data, rp.ctypes.data, cap, rn.ctypes.data))
+        encs = [out[int(oo[i]):int(oo[i] + ol[i])].tobytes() for i in range(n)]
+        refmaps = []
+        for i in range(n):
+            m = {}
+            for k in range(int(rn[i])):
+                at = int(offs[i]) + int(rp[i * cap + k])
+                m[int(rh[i * cap + k])] = a[at:at + SEG].tobytes()
+            refmaps.append(m)
+        return encs, refmaps
+
     def decode_chunks(self, encs, window: 'Window' = None):
         """Decode encoded chunks (one stream, this context's cache) on the GPU,
         with `window` as the decoder's BACKREF window (default: the context's).
@@ -801,9 +854,17 @@ class XCodecEncoder:
     def __init__(self, ctx: Context):
         self.ctx = ctx
 
-    def encode(self, data: bytes) -> bytes:
+    def encode(self, data: bytes, refmap: dict = None) -> bytes:
+        """encode(output, input, refmap): with a dict, every hash the call REF'd
+        and not yet in it is added with its segment, in ascending hash order
+        (xcodec/xcodec_encoder.cc:364-371)."""
         if not data:
             return b''
+        if refmap is not None:
+            encs, maps = self.ctx.encode_chunks_refmap(data, np.array([0]), np.array([len(data)]))
+            for h, seg in maps[0].items():
+                refmap.setdefault(h, seg)
+            return encs[0]
         return self.ctx.encode_chunks(data, np.array([0]), np.array([len(data)]), semantics=XCG_SEM_STREAM)[0]
 
 
