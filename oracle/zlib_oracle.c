@@ -20,7 +20,7 @@
  *     build_tree / gen_bitlen / gen_codes, scan_tree / send_tree,
  *     build_bl_tree, send_all_trees, compress_block, _tr_stored_block.
  * It is written in the formulation the GPU kernels use (wanproxy_amd/csrc/
- * xcg_deflate.hip): a call's bytes are hashed at every position, every
+ * xcg_zdeflate*.hip): a call's bytes are hashed at every position, every
  * position's hash chain is walked up front ("match table": best length and
  * first position reaching it, for the full and the quartered chain budget),
  * and a sequential scan then replays deflate_slow's decisions over that

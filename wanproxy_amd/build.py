@@ -19,7 +19,9 @@ SRCS = ['csrc/xcg_encode_stream.hip', 'csrc/xcg_encode_stream_lru.hip', 'csrc/xc
         'csrc/xcg_encode_refmap.hip', 'csrc/xcg_api_encode.hip', 'csrc/xcg_api_decode.hip', 'csrc/xcg_decode.hip',
         'csrc/xcg_decode_bounded.hip', 'csrc/xcg_decode_small.hip',
         'csrc/xcg_decode_indep.hip', 'csrc/xcg_decode_group.hip', 'csrc/xcg_hash.hip', 'csrc/xcg_lru.hip',
-        'csrc/xcg_pair.hip', 'csrc/xcg_cache_bulk.hip', 'csrc/xcg_cache_point.hip', 'csrc/xcg_pipe.cpp', 'csrc/xcg_deflate.hip', 'csrc/xcg_inflate.hip',
+        'csrc/xcg_pair.hip', 'csrc/xcg_cache_bulk.hip', 'csrc/xcg_cache_point.hip', 'csrc/xcg_pipe.cpp',
+        'csrc/xcg_zdeflate.hip', 'csrc/xcg_zdeflate_match.hip', 'csrc/xcg_zdeflate_parse.hip',
+        'csrc/xcg_zdeflate_huff.hip', 'csrc/xcg_inflate.hip',
         'csrc/xcg_pair_state.hip', 'csrc/xcg_volume.cpp']
 HDRS = sorted(glob.glob(os.path.join(HERE, 'csrc', '*.h'))) + ['../include/xcgpu.h']   # every object depends on all
 OUT = os.path.join(HERE, 'libxcgpu.so')

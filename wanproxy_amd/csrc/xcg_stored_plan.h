@@ -1,7 +1,7 @@
 // Level 0 of wanproxy's zlib stage: zlib 1.2.11's deflate() + deflate_stored
 // control flow in DeflatePipe::consume's call pattern (zlib/deflate_pipe.cc:
 // 57-115), over lengths only.  Host code shared by the engine
-// (xcg_deflate.hip: the GPU moves the bytes the plan names) and its CPU test
+// (xcg_zdeflate.hip: the GPU moves the bytes the plan names) and its CPU test
 // (tests/test_zlib_oracle.py runs the plan through oracle/stored_plan_harness.cc
 // and checks it against the system zlib).
 #pragma once
