@@ -578,6 +578,47 @@ int xcg_decode_host(xcg_ctx *ctx, const uint8_t *h_enc, uint64_t enc_len, const 
                     uint64_t *h_out_len, int32_t *h_chunk_status, uint64_t *h_consumed, uint64_t *h_unknown,
                     uint32_t unknown_cap, uint32_t *h_nunknown);
 
+/* Successive decode() calls of SEVERAL decoders on one cache, in one batch:
+ * one XCodecWindow per decoder, one XCodecCache shared by all of them
+ * (xcodec/xcodec_decoder.h, xcodec/xcodec_pipe_pair.cc:182-203) -- the chunks
+ * a proxy received on several pipes from one peer.  Chunk i is a call on
+ * decoder h_chunk_window[i] (a host array): its EXTRACTs and resolved REFs
+ * declare into windows[h_chunk_window[i]], its BACKREFs read that window.
+ * Everything else is xcg_decode_batch's: REFs resolve against the cache as it
+ * stands at that point of the batch, whichever decoder's EXTRACT entered the
+ * segment; name reuse; packed outputs and XCG_EOVERFLOW (*h_total_out = the
+ * size needed) with nothing written; statuses 0 / 1 / 3 / -1; ONE stop point
+ * for the whole batch -- the first unknown REF or BACKREF to an empty slot --
+ * behind which every chunk has status 2, whichever window it names (the caller
+ * presents those again); the EXTRACTs before the stop point are committed.
+ * Each window's cursor advances by the declares its own chunks made before
+ * the stop point; a window no chunk names is not touched.  *h_stop_chunk: the
+ * chunk that holds the stop point, n if there is none.
+ *
+ * decode_skim's set is not produced (present the rest of the stopped chunk to
+ * xcg_decode_batch on its window for it: the cache is as the stop left it),
+ * and no number of distinct unknown hashes makes the call fail.
+ *
+ * XCG_EINVAL, before anything changes: a null pointer, n_windows == 0 or above
+ * XCG_DECODE_WINDOWS_MAX, h_chunk_window[i] >= n_windows, a null window, a
+ * window listed twice or of another device.  XCG_ENOTSUP on bounded and pair
+ * contexts.  n == 0: XCG_OK.  The context's current window
+ * (xcg_decode_set_window) is neither used nor changed.  The call keeps 4 KiB
+ * of device scratch per window on the context. */
+#define XCG_DECODE_WINDOWS_MAX 65536u
+int xcg_decode_batch_windows(xcg_ctx *ctx, const uint8_t *d_enc, const uint64_t *d_chunk_off,
+                             const uint32_t *d_chunk_len, uint32_t n, uint32_t max_chunk_len,
+                             xcg_window *const *windows, uint32_t n_windows, const uint32_t *h_chunk_window,
+                             uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off, uint64_t *d_out_len,
+                             int32_t *d_chunk_status, uint64_t *d_consumed, uint32_t *h_stop_chunk,
+                             uint64_t *h_total_out, void *stream);
+/* Host-memory convenience over xcg_decode_batch_windows. */
+int xcg_decode_host_windows(xcg_ctx *ctx, const uint8_t *h_enc, uint64_t enc_len, const uint64_t *h_chunk_off,
+                            const uint32_t *h_chunk_len, uint32_t n, xcg_window *const *windows,
+                            uint32_t n_windows, const uint32_t *h_chunk_window, uint8_t *h_out, uint64_t out_cap,
+                            uint64_t *h_out_off, uint64_t *h_out_len, int32_t *h_chunk_status,
+                            uint64_t *h_consumed, uint32_t *h_stop_chunk, uint64_t *h_total_out);
+
 /* One XCodecDecoder::decode(output, input, unknown_hashes) call from host
  * memory (xcodec/xcodec_decoder.cc:66-272), the way tack (-d, one call per
  * 64 KiB read, programs/tack/tack.cc:329-359) and XCodecPipePair
@@ -645,6 +686,21 @@ void xcg_pipe_destroy(xcg_pipe *p);
 int xcg_pipe_encoder_consume(xcg_pipe *p, const uint8_t *data, uint64_t len, xcg_pipe_out *out);
 int xcg_pipe_encoder_consume_many(xcg_pipe *const *pipes, const uint8_t *const *data, const uint64_t *len, uint32_t n,
                                   xcg_pipe_out *out);
+/* xcg_pipe_decoder_consume for pipes[0 .. n) in order -- every out[k], every
+ * rc[k] (nullable), the decoder contexts' caches and every pipe's window and
+ * buffered state exactly as that loop leaves them -- with the decode() calls
+ * of consecutive pipes that decode on one unbounded context made in ONE GPU
+ * batch (xcg_decode_host_windows, one window per pipe).  A pipe whose bytes
+ * hold a <LEARN>, a connecting pipe before its <HELLO> and a pipe on a bounded
+ * or pair context are served by the serial call in their place.  A pipe that
+ * fails (XCG_EPROTO) does not stop the others.  Returns the first nonzero
+ * rc[k]; XCG_EINVAL before anything changes for null arguments or a pipe
+ * listed twice; an engine failure at once. */
+int xcg_pipe_decoder_consume_many(xcg_pipe *const *pipes, const uint8_t *const *data, const uint64_t *len, uint32_t n,
+                                  xcg_pipe_out *out, int *rc);
+/* Diagnostics: the batched decode calls xcg_pipe_decoder_consume_many has made
+ * in this process, and the chunks (one per pipe) they held. */
+void xcg_pipe_debug_decode_many(uint64_t out[2]);
 int xcg_pipe_decoder_consume(xcg_pipe *p, const uint8_t *data, uint64_t len, xcg_pipe_out *out);
 /* Frames whose REF segments the encoder still keeps for <ASK> (not yet <ADVANCE>d). */
 uint32_t xcg_pipe_pending_frames(const xcg_pipe *p);

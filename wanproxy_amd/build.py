@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRCS = ['csrc/xcg_encode_stream.hip', 'csrc/xcg_encode_stream_lru.hip', 'csrc/xcg_encode_indep.hip',
         'csrc/xcg_encode_group.hip', 'csrc/xcg_encode_screen.hip', 'csrc/xcg_ctx.hip', 'csrc/xcg_api_cache.hip',
         'csrc/xcg_encode_refmap.hip', 'csrc/xcg_api_encode.hip', 'csrc/xcg_api_decode.hip', 'csrc/xcg_decode.hip',
-        'csrc/xcg_decode_bounded.hip', 'csrc/xcg_decode_small.hip',
+        'csrc/xcg_decode_bounded.hip', 'csrc/xcg_decode_small.hip', 'csrc/xcg_decode_windows.hip',
         'csrc/xcg_decode_indep.hip', 'csrc/xcg_decode_group.hip', 'csrc/xcg_hash.hip', 'csrc/xcg_lru.hip',
         'csrc/xcg_pair.hip', 'csrc/xcg_cache_bulk.hip', 'csrc/xcg_cache_point.hip', 'csrc/xcg_pipe.cpp',
         'csrc/xcg_zdeflate.hip', 'csrc/xcg_zdeflate_match.hip', 'csrc/xcg_zdeflate_parse.hip',

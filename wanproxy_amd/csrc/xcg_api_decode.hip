@@ -15,16 +15,18 @@
 #include "xcg_args.h"
 #include "xcg_cache.h"
 #include "xcg_ctx.h"
+#include "xcg_decode_batch.h"          // WinView
+#include "xcg_decode_windows_plan.h"
 
 using xcg::align_up;
 
 namespace {
-// A decode batch's driver arguments from the context (its cache, scratch and
-// current window, all allocated) and the call.
-XcgDecodeArgs decode_args(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_chunk_off, const uint32_t* d_chunk_len,
-                          uint32_t n, uint32_t max_chunk_len, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off,
-                          uint64_t* d_out_len, int32_t* d_chunk_status, uint64_t* d_consumed) {
-  const xcg_window* w = c->cur_win;
+// A decode batch's driver arguments from the context (its cache and scratch,
+// allocated), the window `w` (null: the call brings its own windows) and the call.
+XcgDecodeArgs decode_args(xcg_ctx* c, const xcg_window* w, const uint8_t* d_enc, const uint64_t* d_chunk_off,
+                          const uint32_t* d_chunk_len, uint32_t n, uint32_t max_chunk_len, uint8_t* d_out,
+                          uint64_t out_cap, uint64_t* d_out_off, uint64_t* d_out_len, int32_t* d_chunk_status,
+                          uint64_t* d_consumed) {
   XcgDecodeArgs a{};
   static_cast<XcgDecodeScratch&>(a) = c->ds;         // every scratch array
   a.in = d_enc; a.chunk_off = d_chunk_off; a.chunk_len = d_chunk_len; a.n = n;
@@ -34,7 +36,7 @@ XcgDecodeArgs decode_args(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_ch
   a.g = c->g;
   a.x_mask = a.x_cap - 1;
   a.unknown_cap = UNKNOWN_CAP;
-  a.win_hash = w->hash; a.win_seg = w->seg; a.win_count = w->count;
+  if (w) { a.win_hash = w->hash; a.win_seg = w->seg; a.win_count = w->count; }
   a.lru = c->bounded ? &c->lru : nullptr;
   a.maxd = max_chunk_len / 2050 + 1;
   a.pair = c->pair;
@@ -66,8 +68,8 @@ int decode_batch_impl(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_chunk_
   }
   if (rc != XCG_OK) return rc;
   xcg_window* w = c->cur_win;
-  const XcgDecodeArgs a = decode_args(c, d_enc, d_chunk_off, d_chunk_len, n, max_chunk_len, d_out, out_cap, d_out_off,
-                                      d_out_len, d_chunk_status, d_consumed);
+  const XcgDecodeArgs a = decode_args(c, w, d_enc, d_chunk_off, d_chunk_len, n, max_chunk_len, d_out, out_cap,
+                                      d_out_off, d_out_len, d_chunk_status, d_consumed);
   if (c->pair) {
     PairGpu G{};
     G.in = d_enc; G.chunk_off = d_chunk_off;
@@ -116,6 +118,83 @@ int decode_batch_impl(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_chunk_
   }
   return XCG_OK;
 }
+
+// xcg_decode_batch_windows without the context's completion mark.
+int decode_windows_impl(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_chunk_off, const uint32_t* d_chunk_len,
+                        uint32_t n, uint32_t max_chunk_len, xcg_window* const* windows, uint32_t n_windows,
+                        const uint32_t* h_chunk_window, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off,
+                        uint64_t* d_out_len, int32_t* d_chunk_status, uint64_t* d_consumed, uint32_t* h_stop_chunk,
+                        uint64_t* h_total_out, hipStream_t stream) {
+  if (!c || (n && (!d_enc || !d_chunk_off || !d_chunk_len || !d_out_off || !d_out_len || !d_chunk_status ||
+                   !d_consumed || !windows || !h_chunk_window)))
+    return XCG_EINVAL;
+  if (h_stop_chunk) *h_stop_chunk = n;
+  if (h_total_out) *h_total_out = 0;
+  if (n == 0) return XCG_OK;
+  if (xcg::dec_windows_distinct((const void* const*)windows, n_windows) != xcg::DEC_PLAN_OK) return XCG_EINVAL;
+  for (uint32_t w = 0; w < n_windows; ++w)
+    if (windows[w]->device != c->device) return XCG_EINVAL;
+  for (uint32_t i = 0; i < n; ++i)
+    if (h_chunk_window[i] >= n_windows) return XCG_EINVAL;
+  if (c->bounded || c->pair) return XCG_ENOTSUP;     // (their classification refuses BACKREFs; serial calls serve them)
+  // the plan, in the pinned block: views | chunk -> window | order | first
+  const size_t nw = n_windows;
+  const size_t o_cw = sizeof(xcg::WinView) * nw, o_ord = o_cw + 4ull * n, o_first = o_ord + 4ull * n,
+               up = align_up(o_first + 4 * (nw + 1), 256);
+  // device only, behind it: t_end words | scan scratch | tail records
+  const size_t o_tend = up, o_scan = align_up(o_tend + 8 * nw, 256), o_tail = align_up(o_scan + 16ull * n, 256),
+               dbytes = o_tail + 16ull * 256 * nw;
+  DeviceGuard g(c->device);
+  ctx_order(c, stream);
+  int rc = ensure_cache(c);
+  if (rc == XCG_OK) rc = ensure_dscratch(c, (uint64_t)n * (max_chunk_len / 2050 + 1));
+  if (rc == XCG_OK) rc = ensure_dchunks(c, n);
+  if (rc != XCG_OK) return rc;
+  const size_t hbytes = up + 8 * nw;
+  if (!c->mem_call.grow_bytes(&c->win_h, &c->win_h_cap, hbytes, xcg::MEM_PINNED) ||
+      !c->mem_call.grow_bytes(&c->win_d, &c->win_d_cap, dbytes, xcg::MEM_DEV))
+    return XCG_ENOMEM;
+  uint8_t* hm = c->win_h;
+  uint8_t* dm = c->win_d;
+  xcg::WinView* hv = (xcg::WinView*)hm;
+  for (uint32_t w = 0; w < n_windows; ++w) {
+    hv[w] = xcg::WinView{};
+    hv[w].hash = windows[w]->hash;
+    hv[w].seg = windows[w]->seg;
+    hv[w].count = windows[w]->count;
+  }
+  memcpy(hm + o_cw, h_chunk_window, 4ull * n);
+  if (xcg::dec_windows_plan(h_chunk_window, n, n_windows, (uint32_t*)(hm + o_ord), (uint32_t*)(hm + o_first)) !=
+      xcg::DEC_PLAN_OK)
+    return XCG_EINVAL;
+  XcgDecodeWindows W{};
+  W.n_windows = n_windows;
+  W.views = dm;
+  W.chunk_win = (const uint32_t*)(dm + o_cw);
+  W.order = (const uint32_t*)(dm + o_ord);
+  W.first = (const uint32_t*)(dm + o_first);
+  W.w_tend = (uint64_t*)(dm + o_tend);
+  W.scan_tmp = (uint64_t*)(dm + o_scan);
+  W.tail = (uint4*)(dm + o_tail);
+  if (hipMemcpyAsync(dm, hm, up, hipMemcpyHostToDevice, stream) != hipSuccess) return XCG_EHIP;
+  XcgDecodeArgs a = decode_args(c, nullptr, d_enc, d_chunk_off, d_chunk_len, n, max_chunk_len, d_out, out_cap,
+                                d_out_off, d_out_len, d_chunk_status, d_consumed);
+  a.no_window = 0;
+  a.wins = &W;
+  uint64_t total = 0, blockp = 0, berr = 0;
+  uint32_t nunk = 0;                                 // (how many hashes are unknown does not matter here)
+  const int lrc = xcg_launch_decode(&a, &total, &blockp, &berr, &nunk, stream);
+  if (h_total_out) *h_total_out = total;
+  if (lrc != 0) return status_of(lrc);               // (XCG_RC_HIP or _OVERFLOW: nothing was written)
+  uint64_t* h_tend = (uint64_t*)(hm + up);
+  if (hipMemcpyAsync(h_tend, W.w_tend, 8 * nw, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+      hipStreamSynchronize(stream) != hipSuccess)
+    return XCG_EHIP;
+  for (uint32_t w = 0; w < n_windows; ++w) windows[w]->count += h_tend[w];   // each decoder's cursor advances
+  const uint64_t stop = blockp < berr ? blockp : berr;
+  if (h_stop_chunk) *h_stop_chunk = stop == ~0ull ? n : (uint32_t)(stop >> 32);
+  return XCG_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -132,6 +211,77 @@ int xcg_decode_batch(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_chunk_o
     ctx_mark(c, (hipStream_t)stream);
   }
   return rc;
+}
+
+int xcg_decode_batch_windows(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_chunk_off,
+                             const uint32_t* d_chunk_len, uint32_t n, uint32_t max_chunk_len,
+                             xcg_window* const* windows, uint32_t n_windows, const uint32_t* h_chunk_window,
+                             uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off, uint64_t* d_out_len,
+                             int32_t* d_chunk_status, uint64_t* d_consumed, uint32_t* h_stop_chunk,
+                             uint64_t* h_total_out, void* stream) {
+  const int rc = decode_windows_impl(c, d_enc, d_chunk_off, d_chunk_len, n, max_chunk_len, windows, n_windows,
+                                     h_chunk_window, d_out, out_cap, d_out_off, d_out_len, d_chunk_status,
+                                     d_consumed, h_stop_chunk, h_total_out, (hipStream_t)stream);
+  if (c) {
+    DeviceGuard g(c->device);
+    ctx_mark(c, (hipStream_t)stream);
+  }
+  return rc;
+}
+
+int xcg_decode_host_windows(xcg_ctx* c, const uint8_t* h_enc, uint64_t enc_len, const uint64_t* h_chunk_off,
+                            const uint32_t* h_chunk_len, uint32_t n, xcg_window* const* windows, uint32_t n_windows,
+                            const uint32_t* h_chunk_window, uint8_t* h_out, uint64_t out_cap, uint64_t* h_out_off,
+                            uint64_t* h_out_len, int32_t* h_chunk_status, uint64_t* h_consumed,
+                            uint32_t* h_stop_chunk, uint64_t* h_total_out) {
+  if (!c || (n && (!h_enc || !h_chunk_off || !h_chunk_len || !h_out_off || !h_out_len || !h_chunk_status ||
+                   !h_consumed || !windows || !h_chunk_window || (out_cap && !h_out))))
+    return XCG_EINVAL;
+  if (h_stop_chunk) *h_stop_chunk = n;
+  if (h_total_out) *h_total_out = 0;
+  if (n == 0) return XCG_OK;
+  uint32_t maxlen = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (h_chunk_off[i] + h_chunk_len[i] > enc_len) return XCG_EINVAL;
+    if (h_chunk_len[i] > maxlen) maxlen = h_chunk_len[i];
+  }
+  DeviceGuard g(c->device);
+  // staging as xcg_decode_host's: [off n][oo n][ol n][cons n][len n][status n] | input | output
+  const size_t meta = align_up(40ull * n, 256), inb = align_up(enc_len ? enc_len : 1, 256),
+               outb = align_up(out_cap ? out_cap : 1, 256);
+  int rc = ensure_stage(c, meta + inb + outb, meta + inb + outb);
+  if (rc != XCG_OK) return rc;
+  uint8_t* hm = c->stage_h;
+  uint8_t* dm = c->stage_d;
+  memcpy(hm, h_chunk_off, 8ull * n);
+  memcpy(hm + 32ull * n, h_chunk_len, 4ull * n);
+  memcpy(hm + meta, h_enc, enc_len);
+  const hipStream_t st = c->call_st;
+  uint64_t* d_oo = (uint64_t*)(dm + 8ull * n);
+  uint64_t* d_ol = (uint64_t*)(dm + 16ull * n);
+  uint64_t* d_cons = (uint64_t*)(dm + 24ull * n);
+  int32_t* d_st = (int32_t*)(dm + 36ull * n);
+  uint8_t* d_out = dm + meta + inb;
+  if (hipMemcpyAsync(dm, hm, meta + enc_len, hipMemcpyHostToDevice, st) != hipSuccess) return XCG_EHIP;
+  uint64_t total = 0;
+  rc = xcg_decode_batch_windows(c, dm + meta, (const uint64_t*)dm, (const uint32_t*)(dm + 32ull * n), n, maxlen,
+                                windows, n_windows, h_chunk_window, d_out, out_cap, d_oo, d_ol, d_st, d_cons,
+                                h_stop_chunk, &total, st);
+  if (h_total_out) *h_total_out = total;
+  if (rc != XCG_OK) return rc;
+  uint8_t* ho = hm + meta + inb;
+  const uint64_t nout = total < out_cap ? total : out_cap;
+  if (hipMemcpyAsync(hm + 8ull * n, dm + 8ull * n, 24ull * n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(hm + 36ull * n, d_st, 4ull * n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      (nout && hipMemcpyAsync(ho, d_out, nout, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+      hipStreamSynchronize(st) != hipSuccess)
+    return XCG_EHIP;
+  memcpy(h_out_off, hm + 8ull * n, 8ull * n);
+  memcpy(h_out_len, hm + 16ull * n, 8ull * n);
+  memcpy(h_consumed, hm + 24ull * n, 8ull * n);
+  memcpy(h_chunk_status, hm + 36ull * n, 4ull * n);
+  if (nout) memcpy(h_out, ho, nout);
+  return XCG_OK;
 }
 
 int xcg_decode_batch_independent(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_chunk_off,

@@ -267,6 +267,19 @@ struct XcgDecodeScratch {
   uint4* d_tail = nullptr;         // 256 declare records (window update)
 };
 
+// A batch over several BACKREF windows (xcg_decode_batch_windows): the plan of
+// xcg_decode_windows_plan.h and the windows' scratch, all device memory.
+struct XcgDecodeWindows {
+  uint32_t n_windows;
+  void* views;               // xcg::WinView[n_windows]: hash, seg and count filled by the host
+  const uint32_t* chunk_win; // [n] chunk -> window
+  const uint32_t* order;     // [n] the chunks window-major
+  const uint32_t* first;     // [n_windows + 1] each window's first position in `order`
+  uint64_t* scan_tmp;        // [2 n] the declare counts in that order, and their scan
+  uint64_t* w_tend;          // [n_windows] out: each window's declares before the stop point
+  uint4* tail;               // [256 * n_windows] tail records
+};
+
 // Arguments of the batch decode driver (xcg_launch_decode): the context's
 // decode scratch and the call.
 struct XcgDecodeArgs : XcgDecodeScratch {
@@ -292,6 +305,7 @@ struct XcgDecodeArgs : XcgDecodeScratch {
   XcgPairState* pair;    // XCodecCachePair (null: not a pair)
   int no_window;         // the BACKREF window is left alone (<LEARN>, single-segment host calls)
   uint32_t dup_cap;      // x_cap / 2
+  const XcgDecodeWindows* wins;   // one window per decoder (null: win_hash / win_seg / win_count)
 };
 
 // Arguments of the independent decode driver (xcg_launch_decode_independent):
@@ -425,3 +439,5 @@ extern "C" int xcg_launch_decode_small(const uint8_t* in, uint32_t len, const Xc
 // (connect_hold: xcg_ctx_connect with the hold taken under the registry lock)
 extern "C" int xcg_ctx_connect_hold(xcg_ctx* parent, const char* uuid36, xcg_ctx** out);
 extern "C" void xcg_registry_release(xcg_ctx* c);
+// (xcg_ctx.hip for xcg_pipe.cpp) neither a bounded cache nor a pair: xcg_decode_batch_windows takes it
+extern "C" int xcg_ctx_unbounded(const xcg_ctx* c);

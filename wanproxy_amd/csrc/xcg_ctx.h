@@ -76,6 +76,11 @@ struct xcg_ctx {
   uint8_t* zc_h = nullptr;
   size_t zc_cap = 0;
   uint32_t zc_seq = 0;
+  // xcg_decode_batch_windows: the plan and the windows' scratch (device), and
+  // the pinned block the plan goes up from and the t_end words come back to
+  uint8_t* win_d = nullptr;
+  uint8_t* win_h = nullptr;
+  size_t win_d_cap = 0, win_h_cap = 0;
   // Who frees what (xcg_devmem.h): the cache, the LRU arrays, the batch and decode scratch (each
   // regrown as a whole), and the call blocks -- status words, staging, zero-copy block
   xcg::DevMem mem_cache, mem_lru, mem_bs, mem_ds, mem_call;

@@ -640,6 +640,8 @@ void xcg_debug_mem_live(uint64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = xcg::HipMem::live[i].load();
 }
 
+int xcg_ctx_unbounded(const xcg_ctx* c) { return c && !c->bounded && !c->pair; }
+
 int xcg_ctx_flags(const xcg_ctx* c, uint32_t* flags) {
   if (!c || !flags) return XCG_EINVAL;
   *flags = c->flags;

@@ -69,7 +69,9 @@ namespace xcg {
 
 // ------------------------------------------------------------------ kernels
 
-template <bool EMIT, bool REUSE = false>
+// WINS: one window per decoder (xcg_decode_windows.hip) -- a BACKREF reads the
+// window its chunk names; everything else is the one-window kernel.
+template <bool EMIT, bool REUSE = false, bool WINS = false>
 __global__ __launch_bounds__(256) void decode_kernel(DecParams prm) {
   const int wv = (int)readfirst(threadIdx.x >> 6);
   const uint32_t chunk = blockIdx.x * 4u + (uint32_t)wv;
@@ -171,6 +173,11 @@ __global__ __launch_bounds__(256) void decode_kernel(DecParams prm) {
         if (spos(chunk, i) >= blockp) { st = -1; i += 3; break; }   // empty slot: moveout precedes the check
         uint64_t h = 0, gd = 0;
         const uint8_t* src = nullptr;
+        if (WINS) {
+          if (!window_slot_of(ManyWindow(prm, readfirst(prm.chunk_win[chunk])), dbase + ndecl, x[i + 2], h, src, gd)) {
+            st = -1; i += 3; break;
+          }
+        } else
         if (!window_slot(prm, dbase + ndecl, x[i + 2], h, src, gd)) { st = -1; i += 3; break; }
         wave_copy2048(out + olen, src);
       }
@@ -206,32 +213,11 @@ __global__ __launch_bounds__(256) void decl_record_kernel(DecParams prm, uint64_
   const uint64_t hi_t = prm.D_tail ? readfirst64(*prm.t_end) : total, lo_t = d_lo_of(prm);
   const uint64_t base = prm.decl_base[chunk], cnt = prm.n_decl[chunk];
   if (base >= hi_t || base + cnt <= lo_t) return;
-  const uint8_t* x = prm.in + prm.chunk_off[chunk];
-  const uint32_t len = prm.chunk_len[chunk];
-  uint64_t t = base;                                         // (the walk stops once the records reach hi_t)
-  walk_op_headers(
-      x, len, chunk,
-      [&](uint32_t i) {
-        if (t >= lo_t) {
-          const uint2 h = dec_window_hash(x + i + 2);
-          const uint64_t src = (uint64_t)(x + i + 2);
-          if (lane_id() == 0) prm.D[t - lo_t] = make_uint4(readfirst(h.x), readfirst(h.y), (uint32_t)src, (uint32_t)(src >> 32));
-        }
-        return ++t >= hi_t;
-      },
-      [&](uint32_t, uint32_t r, uint64_t h, uint64_t here) {
-        const uint64_t tl = t + (uint64_t)lane_id();
-        if ((uint32_t)lane_id() < r && tl >= lo_t && tl < hi_t) {
-          const uint64_t src = (uint64_t)ref_source_t<REUSE>(prm, (uint32_t)h, (uint32_t)(h >> 32), here);
-          prm.D[tl - lo_t] = make_uint4((uint32_t)h, (uint32_t)(h >> 32), (uint32_t)src, (uint32_t)(src >> 32));
-        }
-        t += r;
-        return t >= hi_t;
-      },
-      [](uint32_t) { return false; });
+  decl_record_chunk<REUSE>(prm, chunk, base, lo_t, hi_t, 0 - lo_t);
 }
 
 // Invalid BACKREFs (empty window slot): the first one stops the stream.
+template <bool WINS>
 __global__ __launch_bounds__(256) void decode_brefcheck_kernel(DecParams prm) {
   const int wv = (int)readfirst(threadIdx.x >> 6);
   const uint32_t chunk = blockIdx.x * 4u + (uint32_t)wv;
@@ -257,7 +243,9 @@ __global__ __launch_bounds__(256) void decode_brefcheck_kernel(DecParams prm) {
       if (len - i < 3u) break;
       uint64_t h = 0, gd = 0;
       const uint8_t* src = nullptr;
-      if (!window_slot(prm, t, x[i + 2], h, src, gd)) {
+      const bool live = WINS ? window_slot_of(ManyWindow(prm, readfirst(prm.chunk_win[chunk])), t, x[i + 2], h, src, gd)
+                             : window_slot(prm, t, x[i + 2], h, src, gd);
+      if (!live) {
         if (lane_id() == 0) atomicMin((unsigned long long*)prm.berr_pos, (unsigned long long)spos(chunk, i));
         break;
       }
@@ -641,6 +629,11 @@ xcg::DecParams dec_params(const XcgDecodeArgs* a) {
   p.win_hash = a->win_hash;
   p.win_seg = a->win_seg;
   p.win_count = a->win_count;
+  if (a->wins) {
+    p.wins = (WinView*)a->wins->views;
+    p.chunk_win = a->wins->chunk_win;
+    p.w_tend = a->wins->w_tend;
+  }
   return p;
 }
 }  // namespace
@@ -670,8 +663,9 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
     return XCG_RC_HIP;
   // scan, then number the declares
   hipLaunchKernelGGL(decode_kernel<false>, grid, block, 0, stream, p);
-  hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, stream, (const uint64_t*)p.n_decl,
-                     (uint64_t*)p.decl_base, n, &d->n_decl);
+  if (a->wins) dec_windows_number(a->wins, p, &d->n_decl, stream);   // (per window)
+  else hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, stream, (const uint64_t*)p.n_decl,
+                          (uint64_t*)p.decl_base, n, &d->n_decl);
   hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, stream, (const uint64_t*)p.n_bref,
                      p.n_decl_emit, n, &d->n_bref);              // (n_decl_emit: scratch output here)
   seg1.end();
@@ -708,11 +702,15 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
     p.D = dfull;
     p.D_lo = 0;
     p.D_tail = false;
-    hipLaunchKernelGGL(decl_record_kernel<false>, grid, block, 0, stream, p, ndecl);
+    if (a->wins) dec_windows_records(p, false, stream);
+    else hipLaunchKernelGGL(decl_record_kernel<false>, grid, block, 0, stream, p, ndecl);
   }
   DecTimer seg2(stream, &g_dt_step);
   hipLaunchKernelGGL(decode_refcheck_kernel, grid, block, 0, stream, p);
-  if (nbref > 0) hipLaunchKernelGGL(decode_brefcheck_kernel, grid, block, 0, stream, p);
+  if (nbref > 0) {
+    if (a->wins) hipLaunchKernelGGL(decode_brefcheck_kernel<true>, grid, block, 0, stream, p);
+    else hipLaunchKernelGGL(decode_brefcheck_kernel<false>, grid, block, 0, stream, p);
+  }
   hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, stream, (const uint64_t*)a->out_len, a->out_off,
                      n, &d->total_out);
   if (classified) dec_launch_precheck(p, stream);
@@ -766,23 +764,36 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
     h->reuse[2] = 1;
     // (BACKREFs: the records made before the sizing pass carry the earliest
     // EXTRACT as a flagged REF's source; the hashes, all the checks read, stand)
-    if (dfull) hipLaunchKernelGGL(decl_record_kernel<true>, grid, block, 0, stream, p, ndecl);
+    if (dfull) {
+      if (a->wins) dec_windows_records(p, true, stream);
+      else hipLaunchKernelGGL(decl_record_kernel<true>, grid, block, 0, stream, p, ndecl);
+    }
   }
   DecTimer seg3(stream, &g_dt_step), emit(stream, &g_dt_emit);
   // No stop point: the declares end at ndecl, so the window's tail is known
   // now and the emit pass records it (no second walk over the ops).
-  const bool fuse_tail = !a->no_window && !dfull && *block_pos_out == ~0ull && *berr_pos_out == ~0ull;
+  // (Several windows: every tail comes from dec_windows_finish's record pass.)
+  const bool fuse_tail = !a->wins && !a->no_window && !dfull && *block_pos_out == ~0ull && *berr_pos_out == ~0ull;
   if (fuse_tail) {
     p.tail_D = a->d_tail;
     p.tail_hi = ndecl;
     p.tail_lo = ndecl > 256u ? ndecl - 256u : 0u;
   }
-  if (nconf) hipLaunchKernelGGL((decode_kernel<true, true>), grid, block, 0, stream, p);
-  else hipLaunchKernelGGL((decode_kernel<true, false>), grid, block, 0, stream, p);
+  if (a->wins) {
+    if (nconf) hipLaunchKernelGGL((decode_kernel<true, true, true>), grid, block, 0, stream, p);
+    else hipLaunchKernelGGL((decode_kernel<true, false, true>), grid, block, 0, stream, p);
+  } else {
+    if (nconf) hipLaunchKernelGGL((decode_kernel<true, true>), grid, block, 0, stream, p);
+    else hipLaunchKernelGGL((decode_kernel<true, false>), grid, block, 0, stream, p);
+  }
   emit.end();
   p.tail_D = nullptr;
-  hipLaunchKernelGGL(decode_tend_kernel, dim3(1), dim3(1), 0, stream, p, ndecl);
-  if (!a->no_window) {
+  if (a->wins) {
+    dec_windows_finish(a->wins, p, dfull != nullptr, nconf != 0, stream);
+  } else {
+    hipLaunchKernelGGL(decode_tend_kernel, dim3(1), dim3(1), 0, stream, p, ndecl);
+  }
+  if (!a->wins && !a->no_window) {
     if (!dfull) {
       p.D = a->d_tail;
       p.D_tail = true;

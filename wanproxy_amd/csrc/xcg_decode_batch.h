@@ -12,6 +12,8 @@
 
 namespace xcg {
 
+struct WinView;
+
 struct DecParams {
   const uint8_t* in;           // encoded chunks
   const uint64_t* chunk_off;
@@ -65,6 +67,25 @@ struct DecParams {
   const uint64_t* ptime;
   uint64_t* u_keys;            // unknown-hash set (EMPTY_KEY = free)
   uint32_t u_mask;
+  // ---- one window per decoder (xcg_decode_windows.hip; null on the one-window
+  // path).  decl_base is then each chunk's base among its own window's
+  // declares, and D holds the records window-major (full: window w's declare t
+  // at wins[w].first + t) or 256 per window (tail: at 256 w + t - lo_w).
+  WinView* wins;               // [n_windows]
+  const uint32_t* chunk_win;   // chunk -> window
+  uint64_t* w_tend;            // [n_windows] declares of each window before the stop point
+};
+
+// One decoder's window for the kernels that take several: hash[256], seg[256 *
+// SEG], the declares made before this batch; (device) the window-major index
+// of its first declare of this batch and how many the batch holds.
+struct WinView {
+  uint64_t* hash;
+  uint8_t* seg;
+  uint64_t count;
+  uint64_t first;
+  uint64_t total;
+  uint64_t reserved;
 };
 
 // Insert h into an open-addressed set; true if it was not there.  A full set
@@ -154,6 +175,59 @@ __device__ bool window_slot(const DecParams& prm, uint64_t T, uint32_t c, uint64
   bool dup = false;
   for (uint64_t t = a + lane_id(); t < b; t += 64) {
     const uint4 e = prm.D[t - DL];
+    dup |= e.x == (uint32_t)h && e.y == (uint32_t)(h >> 32);
+  }
+  return ballot(dup) == 0;
+}
+
+// Window w of a batch over several (xcg_decode_batch_windows; wave-uniform w):
+// its state before the batch and its own range of the declare records.
+struct ManyWindow {
+  uint64_t* hash;
+  uint8_t* seg;
+  uint64_t count;
+  const uint4* D;
+  uint64_t off;                // the window's declare t of this batch at D[t + off] (mod 2^64)
+  __device__ __forceinline__ ManyWindow(const DecParams& p, uint32_t w) {
+    const WinView* v = p.wins + w;
+    hash = (uint64_t*)readfirst64((uint64_t)v->hash);
+    seg = (uint8_t*)readfirst64((uint64_t)v->seg);
+    count = readfirst64(v->count);
+    D = p.D;
+    if (p.D_tail) {
+      const uint64_t te = readfirst64(p.w_tend[w]);
+      off = 256ull * w - (te > 256u ? te - 256u : 0u);
+    } else {
+      off = readfirst64(v->first);
+    }
+  }
+};
+
+// window_slot for one of several windows: T and `gd` count the window's own
+// declares, and the records searched are the window's own.  (The slot
+// arithmetic is window_slot's, restated rather than shared: the one-window
+// kernels keep the code they were compiled to before this path existed.)
+__device__ bool window_slot_of(const ManyWindow& win, uint64_t T, uint32_t c, uint64_t& h, const uint8_t*& src,
+                               uint64_t& gd) {
+  const uint64_t W = win.count, G = W + T;
+  if (G == 0) return false;
+  const uint64_t r = (G - 1u - c) & 255u;
+  if (r > G - 1u) return false;
+  const uint64_t g = G - 1u - r;
+  gd = g;
+  if (g < W) {
+    h = readfirst64(win.hash[c]);
+    if (h == 0) return false;
+    src = win.seg + (uint64_t)c * SEG;
+  } else {
+    const uint4 rec = win.D[g - W + win.off];
+    h = ((uint64_t)readfirst(rec.y) << 32) | readfirst(rec.x);
+    src = (const uint8_t*)(((uint64_t)readfirst(rec.w) << 32) | readfirst(rec.z));
+  }
+  const uint64_t a = (g + 1u > W ? g + 1u - W : 0u), b = T;
+  bool dup = false;
+  for (uint64_t t = a + lane_id(); t < b; t += 64) {
+    const uint4 e = win.D[t + win.off];
     dup |= e.x == (uint32_t)h && e.y == (uint32_t)(h >> 32);
   }
   return ballot(dup) == 0;
@@ -298,6 +372,36 @@ __device__ __forceinline__ void walk_op_headers(const uint8_t* x, uint32_t len, 
   }
 }
 
+// Declare records of one chunk whose first declare is number `base`: those
+// numbered [lo_t, hi_t) go to prm.D[t + off] (mod 2^64).  One wave.
+template <bool REUSE>
+__device__ __forceinline__ void decl_record_chunk(const DecParams& prm, uint32_t chunk, uint64_t base, uint64_t lo_t,
+                                                  uint64_t hi_t, uint64_t off) {
+  const uint8_t* x = prm.in + prm.chunk_off[chunk];
+  const uint32_t len = prm.chunk_len[chunk];
+  uint64_t t = base;                                         // (the walk stops once the records reach hi_t)
+  walk_op_headers(
+      x, len, chunk,
+      [&](uint32_t i) {
+        if (t >= lo_t) {
+          const uint2 h = dec_window_hash(x + i + 2);
+          const uint64_t src = (uint64_t)(x + i + 2);
+          if (lane_id() == 0) prm.D[t + off] = make_uint4(readfirst(h.x), readfirst(h.y), (uint32_t)src, (uint32_t)(src >> 32));
+        }
+        return ++t >= hi_t;
+      },
+      [&](uint32_t, uint32_t r, uint64_t h, uint64_t here) {
+        const uint64_t tl = t + (uint64_t)lane_id();
+        if ((uint32_t)lane_id() < r && tl >= lo_t && tl < hi_t) {
+          const uint64_t src = (uint64_t)ref_source_t<REUSE>(prm, (uint32_t)h, (uint32_t)(h >> 32), here);
+          prm.D[tl + off] = make_uint4((uint32_t)h, (uint32_t)(h >> 32), (uint32_t)src, (uint32_t)(src >> 32));
+        }
+        t += r;
+        return t >= hi_t;
+      },
+      [](uint32_t) { return false; });
+}
+
 // ---- host entry points between the units (plain host functions, the way the
 // encoder's units reach each other; nobody launches another unit's kernel)
 
@@ -322,5 +426,17 @@ void dec_launch_precheck(const DecParams& p, hipStream_t stream);
 // After the window update: the cache takes the batch (bounded: replaced bytes,
 // then xcg_lru_commit; pair: xcg_pair_decode_commit).
 int dec_classified_commit(const XcgDecodeArgs* a, const DecParams& p, const DecClassified& K, hipStream_t stream);
+
+
+// xcg_decode_windows.hip: the window passes of a batch over several windows
+// (p.wins set).  Numbering: p.n_decl scanned in the plan's window-major order
+// into p.decl_base (each chunk's base within its own window), every window's
+// first and total, the batch's total into *d_total.
+void dec_windows_number(const XcgDecodeWindows* w, const DecParams& p, uint64_t* d_total, hipStream_t stream);
+// Records of every declare, window-major (the batch holds BACKREFs).
+void dec_windows_records(const DecParams& p, bool reuse, hipStream_t stream);
+// After the emit pass: every window's t_end, (tail: p.D = the 256 records per
+// window, made here) and the update of every window the batch declared into.
+void dec_windows_finish(const XcgDecodeWindows* w, DecParams& p, bool full, bool reuse, hipStream_t stream);
 
 }  // namespace xcg

@@ -14,13 +14,17 @@
 // finished frames with <ADVANCE>.  The codec work -- every encode and decode --
 // runs on the GPU through xcg_encode_host_refmap / xcg_decode_host; pipes that share
 // an encoder context (one codec, one cache) can be encoded in one GPU batch
-// (xcg_pipe_encoder_consume_many), in the order the reference's single event
-// thread would have served them.
+// (xcg_pipe_encoder_consume_many), and pipes that share a decoder context (one
+// peer's cache) decoded in one (xcg_pipe_decoder_consume_many, over
+// xcg_decode_host_windows: one BACKREF window per pipe), both in the order the
+// reference's single event thread would have served them.
 #include <stdint.h>
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <deque>
+#include <functional>
 #include <memory>
 #include <set>
 #include <unordered_map>
@@ -134,7 +138,11 @@ struct xcg_pipe {
     o->peer_eos = peer_eos;
   }
   int decode_ops();
+  void ack_eos();
   int decode_data();
+  int apply_decoded(int32_t st, uint64_t cons, const uint8_t* out, uint64_t out_len, const uint64_t* unk,
+                    uint32_t nunk);
+  void settle(int rc);
 };
 
 // decoder_decode (:168-433): process pipe ops until the buffer is empty or an
@@ -253,12 +261,16 @@ int xcg_pipe::decode_ops() {
 }
 
 // decoder_decode_data (:435-547): decode the buffered frame bytes on the GPU.
+void xcg_pipe::ack_eos() {
+  if (decoder_received_eos && !encoder_sent_eos_ack) {
+    to_peer.push_back(OP_EOS_ACK);
+    encoder_sent_eos_ack = true;
+  }
+}
+
 int xcg_pipe::decode_data() {
   if (fbuf.empty()) {
-    if (decoder_received_eos && !encoder_sent_eos_ack) {
-      to_peer.push_back(OP_EOS_ACK);
-      encoder_sent_eos_ack = true;
-    }
+    ack_eos();
     return XCG_OK;
   }
   // One decode() call over everything buffered, into an output sized from
@@ -277,6 +289,14 @@ int xcg_pipe::decode_data() {
                          unk.data(), (uint32_t)unk.size(), &nunk);
   xcg_decode_set_window(dec, nullptr);
   if (rc != XCG_OK) return rc;
+  return apply_decoded(st, cons, out.get() + oo, ol, unk.data(), nunk);
+}
+
+// What decoder_decode_data does with a decode() call's result: <ADVANCE>, the
+// decoded bytes, the unknown hashes and their <ASK>s.  (The single call above
+// and xcg_pipe_decoder_consume_many's batch both end here.)
+int xcg_pipe::apply_decoded(int32_t st, uint64_t cons, const uint8_t* out, uint64_t out_len, const uint64_t* unk,
+                            uint32_t nunk) {
   if (st < 0) return XCG_EPROTO;                                     // decode() returned false
   // <ADVANCE> for every frame consumed in full (:460-490)
   uint64_t consumed = cons;
@@ -298,7 +318,7 @@ int xcg_pipe::decode_data() {
     }
     fbuf.erase(fbuf.begin(), fbuf.begin() + (ptrdiff_t)cons);
   }
-  to_local.insert(to_local.end(), out.get() + oo, out.get() + oo + ol);
+  to_local.insert(to_local.end(), out, out + out_len);
   for (uint32_t k = 0; k < nunk; ++k) unknown.insert(unk[k]);
   // <ASK>s in groups of ASK_MAX (:510-545)
   std::vector<uint64_t> hs(unknown.begin(), unknown.end());
@@ -310,6 +330,73 @@ int xcg_pipe::decode_data() {
   }
   return XCG_OK;
 }
+
+// The end of decoder_consume (:125-159): with everything buffered consumed,
+// the EOS hand-overs.
+void xcg_pipe::settle(int rc) {
+  if (rc != XCG_OK || !dbuf.empty() || !fbuf.empty()) return;
+  if (decoder_received_eos && !decoder_sent_eos && unknown.empty()) {
+    local_eos = 1;                                       // decoder_produce_eos (:125-138)
+    decoder_sent_eos = true;
+  }
+  if (encoder_sent_eos_ack && decoder_received_eos_ack && !encoder_produced_eos) {
+    peer_eos = 1;                                        // encoder_produce_eos (:150-159)
+    encoder_produced_eos = true;
+  }
+}
+
+namespace {
+// Side-effect free: would decode_ops over the pipe's pending wire bytes (its
+// buffer plus `data`) reach a <LEARN>?  The walk stops only where decode_ops
+// certainly stops -- an op cut short, a length it refuses, an opcode it does
+// not know -- and walks on over ops it may refuse for the pipe's state, so a
+// <LEARN> it does not see is one decode_ops does not reach either.
+bool reaches_learn(const uint8_t* b, size_t n) {
+  size_t i = 0;
+  while (i < n) {
+    const size_t avail = n - i;
+    const uint8_t op = b[i];
+    if (op == OP_LEARN) return true;
+    if (op == OP_HELLO) {
+      if (avail < 2 || avail < 2u + b[i + 1]) return false;
+      if (b[i + 1] != UUID_LEN || !uuid_ok(b + i + 2)) return false;
+      i += 2 + UUID_LEN;
+    } else if (op == OP_ASK) {
+      if (avail < 3) return false;
+      const uint32_t count = (uint32_t)get_be(b + i + 1, 2);
+      if (count == 0 || count > ASK_MAX || avail < 3 + 8ull * count) return false;
+      i += 3 + 8ull * count;
+    } else if (op == OP_FRAME) {
+      if (avail < 5) return false;
+      const uint32_t len = (uint32_t)get_be(b + i + 1, 4);
+      if (len == 0 || len > MAX_FRAME || avail < 5ull + len) return false;
+      i += 5ull + len;
+    } else if (op == OP_ADVANCE) {
+      if (avail < 5 || get_be(b + i + 1, 4) == 0) return false;
+      i += 5;
+    } else if (op == OP_EOS || op == OP_EOS_ACK) {
+      i += 1;
+    } else {
+      return false;
+    }
+  }
+  return false;
+}
+
+// Diagnostics (xcg_pipe_debug_decode_many): batched decode calls made by
+// xcg_pipe_decoder_consume_many and the chunks in them, process-wide.
+std::atomic<uint64_t> g_many_calls{0}, g_many_chunks{0};
+
+// A pipe xcg_pipe_decoder_consume_many may take into a run (see there).
+bool plain(const xcg_pipe* p, const uint8_t* data, uint64_t len) {
+  if (!p->dec || !xcg_ctx_unbounded(p->dec)) return false;
+  if (len == 0) return true;                             // (peer closed: no byte is looked at)
+  if (p->dbuf.empty()) return !reaches_learn(data, len);
+  std::vector<uint8_t> all(p->dbuf);
+  all.insert(all.end(), data, data + len);
+  return !reaches_learn(all.data(), all.size());
+}
+}  // namespace
 
 extern "C" {
 
@@ -451,18 +538,128 @@ int xcg_pipe_decoder_consume(xcg_pipe* p, const uint8_t* data, uint64_t len, xcg
   p->dbuf.insert(p->dbuf.end(), data, data + len);
   rc = p->decode_ops();
   if (rc == XCG_OK && p->unknown.empty()) rc = p->decode_data();
-  if (rc == XCG_OK && p->dbuf.empty() && p->fbuf.empty()) {
-    if (p->decoder_received_eos && !p->decoder_sent_eos && p->unknown.empty()) {
-      p->local_eos = 1;                                  // decoder_produce_eos (:125-138)
-      p->decoder_sent_eos = true;
-    }
-    if (p->encoder_sent_eos_ack && p->decoder_received_eos_ack && !p->encoder_produced_eos) {
-      p->peer_eos = 1;                                   // encoder_produce_eos (:150-159)
-      p->encoder_produced_eos = true;
-    }
-  }
+  p->settle(rc);
   p->finish(out);
   return rc;
+}
+
+// xcg_pipe_decoder_consume for every pipe in order, with the decode() calls of
+// consecutive pipes on one decoder context in one GPU batch.
+//
+// A pipe is *plain* when its pending wire bytes hold no <LEARN>, it decodes on
+// a context it has already (a connecting pipe past its <HELLO>) and that
+// context is unbounded: its decode_ops touches no cache, so it can run before
+// the pipes in front of it have decoded.  A run is a maximal sequence of
+// consecutive plain pipes on one context; each of its pipes brings at most one
+// chunk, its frame buffer, and the run is one xcg_decode_host_windows call over
+// the pipes' windows.  The batch has one stop point: the pipes before it are
+// done, the stopped pipe takes its consumed prefix and -- blocked on a REF --
+// the single call once more for decode_skim's set (that call blocks on its
+// first op: it consumes and declares nothing), and the pipes behind it are
+// the next batch.  Every other pipe, and a run of one, is the serial call.
+int xcg_pipe_decoder_consume_many(xcg_pipe* const* pipes, const uint8_t* const* data, const uint64_t* len,
+                                  uint32_t n, xcg_pipe_out* out, int* rc_out) {
+  if (n == 0) return XCG_OK;
+  if (!pipes || !data || !len) return XCG_EINVAL;
+  for (uint32_t k = 0; k < n; ++k)
+    if (!pipes[k] || (len[k] && !data[k])) return XCG_EINVAL;
+  {
+    std::vector<const xcg_pipe*> s(pipes, pipes + n);
+    std::sort(s.begin(), s.end(), std::less<const xcg_pipe*>());
+    if (std::adjacent_find(s.begin(), s.end()) != s.end()) return XCG_EINVAL;   // a pipe listed twice
+  }
+  int first = XCG_OK;
+  const auto done = [&](uint32_t k, int rc) {
+    if (rc_out) rc_out[k] = rc;
+    if (rc != XCG_OK && first == XCG_OK) first = rc;
+    if (out) pipes[k]->finish(out + k);
+  };
+  const auto serial = [&](uint32_t k) {
+    done(k, xcg_pipe_decoder_consume(pipes[k], data[k], len[k], out ? out + k : nullptr));
+  };
+  uint32_t k = 0;
+  while (k < n) {
+    xcg_ctx* const ctx = pipes[k]->dec;
+    uint32_t e = k;
+    while (e < n && pipes[e]->dec == ctx && plain(pipes[e], data[e], len[e])) ++e;
+    if (e - k < 2) {
+      serial(k++);
+      continue;
+    }
+    // the run [k, e): every pipe's ops first, then the chunks in batches
+    std::vector<uint32_t> pending;                       // pipes with a chunk to decode
+    for (uint32_t j = k; j < e; ++j) {
+      xcg_pipe* p = pipes[j];
+      p->begin();
+      if (len[j] == 0) {                                 // peer closed (:72-87)
+        if (!p->decoder_sent_eos) {
+          p->decoder_sent_eos = true;
+          p->local_eos = 1;
+        }
+        done(j, XCG_OK);
+        continue;
+      }
+      p->dbuf.insert(p->dbuf.end(), data[j], data[j] + len[j]);
+      const int rc = p->decode_ops();
+      if (rc == XCG_OK && p->unknown.empty() && !p->fbuf.empty()) {
+        pending.push_back(j);
+        continue;
+      }
+      if (rc == XCG_OK && p->unknown.empty()) p->ack_eos();   // (decode_data with nothing buffered)
+      p->settle(rc);
+      done(j, rc);
+    }
+    while (!pending.empty()) {
+      const uint32_t m = (uint32_t)pending.size();
+      if (m == 1) {                                      // the single call
+        xcg_pipe* p = pipes[pending[0]];
+        const int rc = p->decode_data();
+        p->settle(rc);
+        done(pending[0], rc);
+        break;
+      }
+      std::vector<uint64_t> off(m), oo(m), ol(m), cons(m);
+      std::vector<uint32_t> cl(m), cw(m);
+      std::vector<int32_t> st(m);
+      std::vector<xcg_window*> wins(m);
+      uint64_t total = 0, cap = 4096;
+      for (uint32_t i = 0; i < m; ++i) {
+        const xcg_pipe* p = pipes[pending[i]];
+        off[i] = total;
+        cl[i] = (uint32_t)p->fbuf.size();
+        cw[i] = i;
+        wins[i] = p->win;
+        total += cl[i];
+        cap += decoded_bound(p->fbuf.data(), cl[i]);
+      }
+      std::vector<uint8_t> in(total);
+      for (uint32_t i = 0; i < m; ++i) memcpy(in.data() + off[i], pipes[pending[i]]->fbuf.data(), cl[i]);
+      std::unique_ptr<uint8_t[]> dout(new uint8_t[cap]);
+      uint32_t stop = m;
+      const int brc = xcg_decode_host_windows(ctx, in.data(), total, off.data(), cl.data(), m, wins.data(), m,
+                                              cw.data(), dout.get(), cap, oo.data(), ol.data(), st.data(),
+                                              cons.data(), &stop, nullptr);
+      if (brc != XCG_OK) return brc;                     // an engine failure: at once
+      ++g_many_calls;
+      g_many_chunks += m;
+      const uint32_t upto = stop < m ? stop + 1 : m;
+      for (uint32_t i = 0; i < upto; ++i) {
+        xcg_pipe* p = pipes[pending[i]];
+        int rc = p->apply_decoded(st[i], cons[i], dout.get() + oo[i], ol[i], nullptr, 0);
+        if (rc == XCG_OK && st[i] == 1) rc = p->decode_data();   // blocked: decode_skim's set and the <ASK>s
+        p->settle(rc);
+        done(pending[i], rc);
+      }
+      pending.erase(pending.begin(), pending.begin() + upto);
+    }
+    k = e;
+  }
+  return first;
+}
+
+void xcg_pipe_debug_decode_many(uint64_t out[2]) {
+  out[0] = g_many_calls;
+  out[1] = g_many_chunks;
 }
 
 uint32_t xcg_pipe_pending_frames(const xcg_pipe* p) { return p ? (uint32_t)p->ref_frames.size() : 0u; }

@@ -137,6 +137,13 @@ def lib():
     L.xcg_decode_batch.argtypes = [vp, u8p, u64p, u32p, C.c_uint32, C.c_uint32, u8p, C.c_uint64, u64p, u64p, vp, u64p,
                                    u64p, C.c_uint32, vp, u64p, vp]
     L.xcg_decode_batch.restype = C.c_int
+    if hasattr(L, 'xcg_decode_batch_windows'):   # (an XCGPU_LIB build from before the windows call: calling it raises)
+        L.xcg_decode_batch_windows.argtypes = [vp, u8p, u64p, u32p, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, u8p,
+                                               C.c_uint64, u64p, u64p, vp, u64p, vp, vp, vp]
+        L.xcg_decode_batch_windows.restype = C.c_int
+        L.xcg_decode_host_windows.argtypes = [vp, u8p, C.c_uint64, u64p, u32p, C.c_uint32, vp, C.c_uint32, vp, u8p,
+                                              C.c_uint64, u64p, u64p, vp, u64p, vp, vp]
+        L.xcg_decode_host_windows.restype = C.c_int
     L.xcg_decode_batch_independent.argtypes = [vp, u8p, u64p, u32p, C.c_uint32, C.c_uint32, u8p, u64p, u64p, u64p, vp,
                                                u64p, u64p, vp]
     L.xcg_decode_batch_independent.restype = C.c_int
@@ -183,6 +190,11 @@ def lib():
                                                 C.c_uint32, C.POINTER(_PipeOut)]
     L.xcg_pipe_encoder_consume_many.restype = C.c_int
     L.xcg_pipe_decoder_consume.argtypes = [vp, C.c_char_p, C.c_uint64, C.POINTER(_PipeOut)]
+    if hasattr(L, 'xcg_pipe_decoder_consume_many'):
+        L.xcg_pipe_decoder_consume_many.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_char_p),
+                                                    C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(_PipeOut),
+                                                    C.POINTER(C.c_int)]
+        L.xcg_pipe_decoder_consume_many.restype = C.c_int
     L.xcg_pipe_decoder_consume.restype = C.c_int
     L.xcg_pipe_pending_frames.argtypes = [vp]
     L.xcg_pipe_pending_frames.restype = C.c_uint32
@@ -576,6 +588,65 @@ class Context:
         outs = [out[int(oo[i]):int(oo[i]) + int(ol[i])].tobytes() if st[i] != 2 else b'' for i in range(n)]
         return outs, st, cons, [int(u) for u in unk[:int(nunk[0])]]
 
+    def decode_chunks_windows(self, chunks, windows, chunk_window, host: bool = False):
+        """Decode encoded chunks that are successive decode() calls of several
+        decoders on this context's cache, in one batch: chunk i declares into
+        and BACKREFs from windows[chunk_window[i]] (Window objects).  Returns
+        (outs, status, consumed, stop_chunk) -- see xcg_decode_batch_windows;
+        host=True goes through xcg_decode_host_windows."""
+        n = len(chunks)
+        lens = np.array([len(e) for e in chunks], dtype=np.uint32)
+        offs = np.zeros(n, dtype=np.uint64)
+        if n > 1:
+            offs[1:] = np.cumsum(lens.astype(np.uint64))[:-1]
+        blob = np.frombuffer(b''.join(chunks) or b'\0', dtype=np.uint8).copy()
+        wins = (C.c_void_p * max(len(windows), 1))(*[w.h if w is not None else None for w in windows])
+        cw = np.ascontiguousarray(chunk_window, dtype=np.uint32)
+        if cw.size != n:
+            raise ValueError('chunk_window: one entry per chunk')
+        cap = int(lens.astype(np.uint64).sum()) * 205 + 4096   # a 10-byte REF expands to 2048
+        stop = np.zeros(1, dtype=np.uint32)
+        total = np.zeros(1, dtype=np.uint64)
+        if host:
+            oo, ol, cons = (np.zeros(n, dtype=np.uint64) for _ in range(3))
+            st = np.zeros(n, dtype=np.int32)
+            for _ in range(2):
+                out = np.zeros(cap, dtype=np.uint8)
+                rc = lib().xcg_decode_host_windows(
+                    self.h, blob.ctypes.data, sum(len(e) for e in chunks), offs.ctypes.data, lens.ctypes.data, n,
+                    wins, len(windows), cw.ctypes.data, out.ctypes.data, cap, oo.ctypes.data, ol.ctypes.data,
+                    st.ctypes.data, cons.ctypes.data, stop.ctypes.data, total.ctypes.data)
+                if rc != XCG_EOVERFLOW:
+                    break
+                cap = int(total[0])            # BACKREF-dense: 3 bytes -> 2048; nothing was committed
+            _check(rc)
+        else:
+            import torch
+            dev = torch.device('cuda', self.device)
+            d_in = torch.from_numpy(blob).to(dev)
+            d_off = torch.from_numpy(offs.view(np.int64)).to(dev)
+            d_len = torch.from_numpy(lens.view(np.int32)).to(dev)
+            d_oo = torch.zeros(n, dtype=torch.int64, device=dev)
+            d_ol = torch.zeros(n, dtype=torch.int64, device=dev)
+            d_st = torch.zeros(n, dtype=torch.int32, device=dev)
+            d_cons = torch.zeros(n, dtype=torch.int64, device=dev)
+            for _ in range(2):
+                d_out = torch.zeros(cap, dtype=torch.uint8, device=dev)
+                rc = lib().xcg_decode_batch_windows(
+                    self.h, C.c_void_p(d_in.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(d_len.data_ptr()),
+                    n, int(lens.max()) if n else 0, wins, len(windows), cw.ctypes.data,
+                    C.c_void_p(d_out.data_ptr()), cap, C.c_void_p(d_oo.data_ptr()), C.c_void_p(d_ol.data_ptr()),
+                    C.c_void_p(d_st.data_ptr()), C.c_void_p(d_cons.data_ptr()), stop.ctypes.data, total.ctypes.data,
+                    _stream_ptr(None))
+                if rc != XCG_EOVERFLOW:
+                    break
+                cap = int(total[0])
+            _check(rc)
+            torch.cuda.synchronize(dev)
+            oo, ol, st, cons, out = (t.cpu().numpy() for t in (d_oo, d_ol, d_st, d_cons, d_out))
+        outs = [out[int(oo[i]):int(oo[i]) + int(ol[i])].tobytes() if st[i] != 2 else b'' for i in range(n)]
+        return outs, st, cons, int(stop[0])
+
     def decode_batch_independent_device(self, d_enc, d_off, d_len, n, max_len, d_out, d_out_off, d_out_cap,
                                         d_out_len, d_status, d_consumed, d_first_unknown=None, stream=None):
         """Raw launch of xcg_decode_batch_independent on device tensors (all torch
@@ -937,6 +1008,30 @@ class PipePair:
         rc = lib().xcg_pipe_decoder_consume(self.h, data, len(data), C.byref(o))
         _check(rc)
         return o.peer(), o.local(), bool(o.local_eos), bool(o.peer_eos)
+
+    @staticmethod
+    def decoder_consume_many(pipes, datas):
+        """decoder_consume(datas[k]) of every pipe in order, the decode() calls of
+        consecutive pipes on one decoder context in one GPU batch
+        (xcg_pipe_decoder_consume_many).  One (to_peer, to_local, local_eos,
+        peer_eos) per pipe, or the XCGError its serial call would have raised;
+        bad arguments (a pipe listed twice) and engine failures raise."""
+        n = len(pipes)
+        hs = (C.c_void_p * n)(*[p.h.value for p in pipes])
+        ds = (C.c_char_p * n)(*datas)
+        ls = (C.c_uint64 * n)(*[len(d) for d in datas])
+        outs = (_PipeOut * n)()
+        rcs = (C.c_int * n)(*([1] * n))                  # (1: not reached)
+        rc = lib().xcg_pipe_decoder_consume_many(hs, ds, ls, n, outs, rcs)
+        if rc != 0 and (rc not in list(rcs) or 1 in list(rcs)):
+            _check(rc)
+        res = []
+        for k, o in enumerate(outs):
+            if rcs[k] != 0:
+                res.append(XCGError(f'xcgpu: {lib().xcg_strerror(rcs[k]).decode()} ({rcs[k]})'))
+            else:
+                res.append((o.peer(), o.local(), bool(o.local_eos), bool(o.peer_eos)))
+        return res
 
     def pending_frames(self) -> int:
         return int(lib().xcg_pipe_pending_frames(self.h))
