@@ -41,6 +41,9 @@
  *   xcg_zinflate_*
  *       InflatePipe::InflatePipe() / consume(Buffer *) zlib/inflate_pipe.h:33-42,
  *                                                      zlib/inflate_pipe.cc:33-139
+ *   xcg_codec_*
+ *       WANProxyCodecPipePair: XCodecPipePair linked with DeflatePipe / InflatePipe
+ *                                   programs/wanproxy/wanproxy_codec_pipe_pair.cc:76-196
  */
 #ifndef XCGPU_H
 #define XCGPU_H
@@ -373,6 +376,11 @@ int xcg_encode_host(xcg_ctx *ctx, int semantics, const uint8_t *h_in, uint64_t i
  * (host arrays of the same shapes, all non-null): the call above runs on the
  * context's staging before the outputs are copied back, and the entries come
  * back in the same synchronisation as the lengths.
+ * xcg_encode_host_refmap_device is that call ended after its first
+ * synchronisation: lengths, status and refmap entries are on the host, and the
+ * encodings stay on the device, chunk i at *d_out + h_out_off[i] (out_cap: the
+ * room the slots take).  *d_out points into the context's staging and is valid
+ * until the context's next host-convenience call (xcg_*_host, xcg_*_call).
  */
 #define XCG_REFMAP_MAX 256u
 int xcg_encode_refmap_batch(xcg_ctx *ctx, const uint8_t *d_enc, const uint64_t *d_enc_off,
@@ -383,6 +391,11 @@ int xcg_encode_host_refmap(xcg_ctx *ctx, int semantics, const uint8_t *h_in, uin
                            const uint64_t *h_chunk_off, const uint32_t *h_chunk_len, uint32_t n, uint8_t *h_out,
                            uint64_t out_cap, const uint64_t *h_out_off, uint64_t *h_out_len,
                            uint64_t *h_ref_hash, uint32_t *h_ref_pos, uint32_t ref_cap, uint32_t *h_ref_count);
+int xcg_encode_host_refmap_device(xcg_ctx *ctx, int semantics, const uint8_t *h_in, uint64_t in_len,
+                                  const uint64_t *h_chunk_off, const uint32_t *h_chunk_len, uint32_t n,
+                                  uint64_t out_cap, const uint64_t *h_out_off, uint64_t *h_out_len,
+                                  uint64_t *h_ref_hash, uint32_t *h_ref_pos, uint32_t ref_cap,
+                                  uint32_t *h_ref_count, const uint8_t **d_out);
 
 /* *h_nref of xcg_encode_call on a cache whose lookups change nothing (an
  * unbounded memory cache, the null cache): no reference list is kept. */
@@ -643,6 +656,19 @@ int xcg_decode_call(xcg_ctx *ctx, const uint8_t *h_in, uint32_t len, uint8_t *h_
 int xcg_pack_outputs(xcg_ctx *ctx, const uint8_t *d_out, const uint64_t *d_out_off, const uint64_t *d_out_len,
                      uint32_t n, uint8_t *d_packed, uint64_t *d_packed_off, uint64_t *d_total, void *stream);
 
+/* Copy n_pieces byte ranges: piece i is d_piece_len[i] bytes from d_src +
+ * d_piece_src_off[i] to d_dst + d_piece_dst_off[i], at any alignment on either
+ * side (a source offset may wrap: the sum is taken as an integer, so a piece
+ * may come from another allocation than d_src).  One wave per (piece, 8 KiB
+ * tile), so a long piece is spread over many waves; 16-byte accesses wherever
+ * the destination allows.  No byte outside a piece is written and none is read
+ * back and rewritten, so pieces may lie back to back; they must not overlap.
+ * max_piece_len sizes the grid (a longer piece is still copied whole).  The
+ * arrays are device memory; asynchronous on `stream`. */
+int xcg_gather_pieces(xcg_ctx *ctx, const uint8_t *d_src, const uint64_t *d_piece_src_off,
+                      const uint64_t *d_piece_dst_off, const uint32_t *d_piece_len, uint32_t n_pieces,
+                      uint32_t max_piece_len, uint8_t *d_dst, void *stream);
+
 /* Status word of the context (sticky; nonzero = an internal overflow happened
  * in an earlier asynchronous call).  Synchronises the context's device. */
 int xcg_ctx_status(xcg_ctx *ctx);
@@ -704,6 +730,83 @@ void xcg_pipe_debug_decode_many(uint64_t out[2]);
 int xcg_pipe_decoder_consume(xcg_pipe *p, const uint8_t *data, uint64_t len, xcg_pipe_out *out);
 /* Frames whose REF segments the encoder still keeps for <ASK> (not yet <ADVANCE>d). */
 uint32_t xcg_pipe_pending_frames(const xcg_pipe *p);
+
+/*
+ * The configured codec: wanproxy.conf's `codec XCodec` with `compressor zlib` /
+ * `compressor_level N` (wanproxy.conf:32-41), as WANProxyCodecPipePair links it
+ * (programs/wanproxy/wanproxy_codec_pipe_pair.cc:76-196): towards the peer the
+ * bytes of XCodecPipePair go through one DeflatePipe (:97-106, 148-157), from
+ * the peer they come through one InflatePipe into the pair.  A codec holds the
+ * encoder context, the decoder context (connect == 0) or the parent its pipes'
+ * decoder contexts connect from at <HELLO> (connect != 0, as
+ * xcg_pipe_create_connect), the compressor level (0-9; -1: no compressor, every
+ * output is the pair's, byte for byte) and up to max_pipes pipes: it owns one
+ * xcg_zdeflate(level, max_pipes) and one xcg_zinflate(max_pipes), and a pipe
+ * takes a free slot of each, reset on creation and returned on destroy
+ * (XCG_ENOMEM: max_pipes pipes are alive).  Destroy the pipes before the codec.
+ *
+ * The chain, call by call (the event system is not part of the engine):
+ *   link rule: everything one upstream consume() produces is ONE downstream
+ *     consume() of one Buffer (PipeProducer::input corks during consume,
+ *     io/pipe/pipe_producer.cc:58-83, 118-143), cut into 2048-byte segments; a
+ *     produce_eos is that buffer first, if not empty, then one empty consume.
+ *   send (len 0 = the local side closed): to_peer is what
+ *     DeflatePipe::consume(W) produces for W = xcg_pipe_encoder_consume's
+ *     to_peer, the 64 KiB flush stop included (zlib/deflate_pipe.cc:57-115): a
+ *     consume may deliver less than it made, and the pipe delivers the rest
+ *     first with its next consume -- the layer keeps those bytes.
+ *   receive, len > 0: InflatePipe::consume(data) (zlib/inflate_pipe.cc:60-139)
+ *     gives W; produce_error fails this pipe with XCG_EPROTO, now and on every
+ *     later call, and nothing reaches its pair (the other pipes of the call are
+ *     served); otherwise a non-empty W is xcg_pipe_decoder_consume's input.
+ *   receive, len == 0 (the peer closed): an empty inflate consume.  If the zlib
+ *     stream had ended (produce_eos) the pair gets its bytes, if any, and then
+ *     its own empty consume; if not, nothing reaches the pair (:113-124).
+ *   Every to_peer of the pair -- the <ASK>, <ADVANCE>, <LEARN>, <EOS_ACK> a
+ *     receive makes too -- goes through the pipe's one deflate stream in call
+ *     order; when a pair call reports peer_eos (encoder_produce_eos) one empty
+ *     DeflatePipe::consume follows (Z_FINISH), its bytes end to_peer.
+ *   to_local and local_eos are the pair's.
+ * The _many calls serve the pipes in the order given: every out[k], rc[k]
+ * (nullable), cache, window, zlib stream and all buffered state end exactly as
+ * the serial loop over the above leaves them.  With a compressor, send_many
+ * is one encode batch and one deflate batch, the wire between them either
+ * composed on the host or kept on the device (xcg_debug_set_codec_fused: one
+ * gather builds every wire in the deflate input); receive_many is one inflate batch, one
+ * xcg_pipe_decoder_consume_many and one deflate batch for the replies.  Outputs
+ * belong to the pipe and stay valid until its next call.  Returns the first
+ * nonzero rc[k]; an engine failure at once.  XCG_EINVAL, before anything
+ * changes: null arguments, a pipe listed twice, pipes of different codecs, a
+ * send on a pipe that already sent EOS, a send whose worst-case wire (<HELLO> +
+ * <EOS> + per frame 5 + xcg_encode_bound(frame length)) passes the deflate
+ * stage's 2^24 bytes a consume, a receive above the inflate stage's 2^26.
+ * xcg_codec_stats: PipeByteCount's four counters -- st[0] local bytes in,
+ * st[1] bytes to the peer after deflate, st[2] bytes from the peer before
+ * inflate, st[3] bytes to the local side.
+ */
+typedef struct xcg_codec xcg_codec;
+typedef struct xcg_codec_pipe xcg_codec_pipe;
+int xcg_codec_create(xcg_ctx *enc, xcg_ctx *dec_or_parent, int connect, int compressor_level, uint32_t max_pipes,
+                     xcg_codec **out);
+void xcg_codec_destroy(xcg_codec *codec);
+int xcg_codec_pipe_create(xcg_codec *codec, const uint8_t *uuid, xcg_codec_pipe **out);
+void xcg_codec_pipe_destroy(xcg_codec_pipe *p);
+/* The XCodecPipePair inside (xcg_pipe_pending_frames, xcg_pipe_decoder_ctx). */
+xcg_pipe *xcg_codec_pipe_pair(const xcg_codec_pipe *p);
+int xcg_codec_send_many(xcg_codec_pipe *const *pipes, const uint8_t *const *data, const uint64_t *len, uint32_t n,
+                        xcg_pipe_out *out, int *rc /* nullable */);
+int xcg_codec_receive_many(xcg_codec_pipe *const *pipes, const uint8_t *const *data, const uint64_t *len, uint32_t n,
+                           xcg_pipe_out *out, int *rc /* nullable */);
+int xcg_codec_stats(const xcg_codec *codec, uint64_t st[4]);
+/* Which send path xcg_codec_send_many takes: 0 (default) the plain host
+ * composition (xcg_pipe_encoder_consume_many's to_peer on the host, then
+ * xcg_zdeflate_host), 1 the path that keeps the wire on the device between the
+ * encoder and deflate; same bytes.  Returns the previous setting. */
+int xcg_debug_set_codec_fused(int on);
+/* Diagnostics, process-wide: send batches that took the device path, send
+ * batches composed on the host, inflate batches, decode batches
+ * (xcg_pipe_decoder_consume_many calls) the codec layer has made. */
+void xcg_codec_debug_counts(uint64_t out[4]);
 
 /*
  * The process-wide cache registry of XCodecCache::connect / enter / lookup

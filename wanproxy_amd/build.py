@@ -20,6 +20,7 @@ SRCS = ['csrc/xcg_encode_stream.hip', 'csrc/xcg_encode_stream_lru.hip', 'csrc/xc
         'csrc/xcg_decode_bounded.hip', 'csrc/xcg_decode_small.hip', 'csrc/xcg_decode_windows.hip',
         'csrc/xcg_decode_indep.hip', 'csrc/xcg_decode_group.hip', 'csrc/xcg_hash.hip', 'csrc/xcg_lru.hip',
         'csrc/xcg_pair.hip', 'csrc/xcg_cache_bulk.hip', 'csrc/xcg_cache_point.hip', 'csrc/xcg_pipe.cpp',
+        'csrc/xcg_codec.cpp', 'csrc/xcg_wire.hip',
         'csrc/xcg_zdeflate.hip', 'csrc/xcg_zdeflate_match.hip', 'csrc/xcg_zdeflate_parse.hip',
         'csrc/xcg_zdeflate_huff.hip', 'csrc/xcg_inflate.hip',
         'csrc/xcg_pair_state.hip', 'csrc/xcg_volume.cpp']
@@ -29,7 +30,7 @@ HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 # Units whose kernels keep their whole parse state in registers: a compiler that spills it
 # to scratch still builds a correct library, several times slower, and no test would notice -- so the build reads
 # these units' resource-usage remarks and refuses a kernel with scratch.
-NO_SCRATCH = ('csrc/xcg_encode_indep.hip', 'csrc/xcg_encode_group.hip')
+NO_SCRATCH = ('csrc/xcg_encode_indep.hip', 'csrc/xcg_encode_group.hip', 'csrc/xcg_wire.hip')
 REMARKS = '-Rpass-analysis=kernel-resource-usage'
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall'] + os.environ.get('XCG_EXTRA_FLAGS', '').split()
 

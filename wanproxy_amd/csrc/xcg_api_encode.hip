@@ -87,7 +87,10 @@ int encode_batch_impl(xcg_ctx* c, int semantics, const uint8_t* d_in, const uint
 }
 
 // xcg_encode_host, and with `rm` xcg_encode_host_refmap: the same call with the
-// refmap launch behind the batch, its rows beside the lengths.
+// refmap launch behind the batch, its rows beside the lengths.  With `d_keep`
+// (xcg_encode_host_refmap_device) the call ends after its first
+// synchronisation: lengths, status and rows are on the host, the encodings stay
+// in the staging's output slots, *d_keep.
 struct HostRefmap {
   uint64_t* hash;
   uint32_t* pos;
@@ -97,8 +100,10 @@ struct HostRefmap {
 
 int encode_host_impl(xcg_ctx* c, int semantics, const uint8_t* h_in, uint64_t in_len, const uint64_t* h_chunk_off,
                      const uint32_t* h_chunk_len, uint32_t n, uint8_t* h_out, uint64_t out_cap,
-                     const uint64_t* h_out_off, uint64_t* h_out_len, const HostRefmap* rm) {
-  if (!c || (n && (!h_in || !h_chunk_off || !h_chunk_len || !h_out || !h_out_off || !h_out_len))) return XCG_EINVAL;
+                     const uint64_t* h_out_off, uint64_t* h_out_len, const HostRefmap* rm,
+                     const uint8_t** d_keep = nullptr) {
+  if (!c || (n && (!h_in || !h_chunk_off || !h_chunk_len || (!h_out && !d_keep) || !h_out_off || !h_out_len)))
+    return XCG_EINVAL;
   if (n == 0) return XCG_OK;
   uint32_t maxlen = 0;
   for (uint32_t i = 0; i < n; ++i) {
@@ -150,7 +155,7 @@ int encode_host_impl(xcg_ctx* c, int semantics, const uint8_t* h_in, uint64_t in
   uint8_t* ho = hm + meta + inb;
   for (uint32_t i = 0; i < n; ++i) {
     h_out_len[i] = ol[i];
-    if (ol[i] && hipMemcpyAsync(ho + h_out_off[i], d_out + h_out_off[i], ol[i], hipMemcpyDeviceToHost, st) != hipSuccess)
+    if (!d_keep && ol[i] && hipMemcpyAsync(ho + h_out_off[i], d_out + h_out_off[i], ol[i], hipMemcpyDeviceToHost, st) != hipSuccess)
       return XCG_EHIP;
   }
   if (rm) {                                          // (entries past a chunk's count stay as the caller left them)
@@ -165,6 +170,10 @@ int encode_host_impl(xcg_ctx* c, int semantics, const uint8_t* h_in, uint64_t in
         memcpy(rm->pos + (uint64_t)i * rm->cap, hp + (uint64_t)i * rm->cap, 4ull * k);
       }
     }
+  }
+  if (d_keep) {
+    *d_keep = d_out;
+    return XCG_OK;
   }
   if (hipStreamSynchronize(st) != hipSuccess) return XCG_EHIP;
   for (uint32_t i = 0; i < n; ++i)
@@ -208,6 +217,18 @@ int xcg_encode_host_refmap(xcg_ctx* c, int semantics, const uint8_t* h_in, uint6
   const HostRefmap rm{h_ref_hash, h_ref_pos, ref_cap, h_ref_count};
   return encode_host_impl(c, semantics, h_in, in_len, h_chunk_off, h_chunk_len, n, h_out, out_cap, h_out_off,
                           h_out_len, &rm);
+}
+
+int xcg_encode_host_refmap_device(xcg_ctx* c, int semantics, const uint8_t* h_in, uint64_t in_len,
+                                  const uint64_t* h_chunk_off, const uint32_t* h_chunk_len, uint32_t n,
+                                  uint64_t out_cap, const uint64_t* h_out_off, uint64_t* h_out_len,
+                                  uint64_t* h_ref_hash, uint32_t* h_ref_pos, uint32_t ref_cap, uint32_t* h_ref_count,
+                                  const uint8_t** d_out) {
+  if (!h_ref_hash || !h_ref_pos || !h_ref_count || !d_out) return XCG_EINVAL;
+  *d_out = nullptr;
+  const HostRefmap rm{h_ref_hash, h_ref_pos, ref_cap, h_ref_count};
+  return encode_host_impl(c, semantics, h_in, in_len, h_chunk_off, h_chunk_len, n, nullptr, out_cap, h_out_off,
+                          h_out_len, &rm, d_out);
 }
 
 int xcg_encode_refmap_batch(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_enc_off, const uint64_t* d_enc_len,
@@ -350,6 +371,15 @@ int xcg_pack_outputs(xcg_ctx* c, const uint8_t* d_out, const uint64_t* d_out_off
   const int rc = xcg_launch_pack(d_out, d_out_off, d_out_len, n, d_packed, d_packed_off, d_total, (hipStream_t)stream);
   ctx_mark(c, (hipStream_t)stream);
   return rc == 0 ? XCG_OK : XCG_EHIP;
+}
+
+int xcg_gather_pieces(xcg_ctx* c, const uint8_t* d_src, const uint64_t* d_piece_src_off,
+                      const uint64_t* d_piece_dst_off, const uint32_t* d_piece_len, uint32_t n_pieces,
+                      uint32_t max_piece_len, uint8_t* d_dst, void* stream) {
+  if (!c || (n_pieces && (!d_piece_src_off || !d_piece_dst_off || !d_piece_len || !d_dst))) return XCG_EINVAL;
+  DeviceGuard g(c->device);
+  return status_of(xcg_launch_gather_pieces(d_src, d_piece_src_off, d_piece_dst_off, d_piece_len, n_pieces,
+                                            max_piece_len, d_dst, (hipStream_t)stream));
 }
 
 int xcg_window_hashes(xcg_ctx* c, const uint8_t* d_x, uint64_t len, uint64_t* d_hash, void* stream) {

@@ -427,6 +427,10 @@ extern "C" void xcg_launch_exclusive_scan(const uint64_t* len, uint64_t* off, ui
                                           hipStream_t stream);
 extern "C" int xcg_launch_pack(const uint8_t* src, const uint64_t* src_off, const uint64_t* len, uint32_t n,
                                uint8_t* dst, uint64_t* dst_off, uint64_t* d_total, hipStream_t stream);
+// (xcg_wire.hip) xcg_gather_pieces: one wave per (piece, 8 KiB tile)
+extern "C" int xcg_launch_gather_pieces(const uint8_t* d_src, const uint64_t* d_src_off, const uint64_t* d_dst_off,
+                                        const uint32_t* d_len, uint32_t n, uint32_t max_len, uint8_t* d_dst,
+                                        hipStream_t stream);
 extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, uint64_t* block_pos_out,
                                  uint64_t* berr_pos_out, uint32_t* nunknown_out, hipStream_t stream);
 extern "C" int xcg_launch_decode_independent(const XcgIndepDecodeArgs* a, hipStream_t stream);
@@ -441,3 +445,5 @@ extern "C" int xcg_ctx_connect_hold(xcg_ctx* parent, const char* uuid36, xcg_ctx
 extern "C" void xcg_registry_release(xcg_ctx* c);
 // (xcg_ctx.hip for xcg_pipe.cpp) neither a bounded cache nor a pair: xcg_decode_batch_windows takes it
 extern "C" int xcg_ctx_unbounded(const xcg_ctx* c);
+// (xcg_ctx.hip for xcg_codec.cpp) the device a context lives on
+extern "C" int xcg_ctx_device(const xcg_ctx* c);

@@ -641,6 +641,7 @@ void xcg_debug_mem_live(uint64_t out[4]) {
 }
 
 int xcg_ctx_unbounded(const xcg_ctx* c) { return c && !c->bounded && !c->pair; }
+int xcg_ctx_device(const xcg_ctx* c) { return c ? c->device : -1; }
 
 int xcg_ctx_flags(const xcg_ctx* c, uint32_t* flags) {
   if (!c || !flags) return XCG_EINVAL;

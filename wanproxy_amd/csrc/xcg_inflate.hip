@@ -28,6 +28,7 @@
 #include "../../include/xcgpu.h"
 #include "xcg_device.h"
 #include "xcg_devmem.h"
+#include "xcg_zdeflate_types.h"   // INFLATE_MAX_CALL_LEN
 
 namespace xcg {
 namespace zi {
@@ -1501,7 +1502,7 @@ int xcg_zinflate_batch(xcg_zinflate* z, const uint8_t* d_in, const uint64_t* h_i
   size_t io = 0;
   uint32_t maxlen = 0;
   for (uint32_t i = 0; i < n; i++) {
-    if (h_stream[i] >= z->nstreams || seen[h_stream[i]] || h_len[i] > (1u << 26)) return XCG_EINVAL;
+    if (h_stream[i] >= z->nstreams || seen[h_stream[i]] || h_len[i] > xcg::zd::INFLATE_MAX_CALL_LEN) return XCG_EINVAL;
     seen[h_stream[i]] = 1;
     ICall& c = calls[i];
     c.in_off = h_in_off[i];

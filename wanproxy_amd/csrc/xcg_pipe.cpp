@@ -17,7 +17,9 @@
 // (xcg_pipe_encoder_consume_many), and pipes that share a decoder context (one
 // peer's cache) decoded in one (xcg_pipe_decoder_consume_many, over
 // xcg_decode_host_windows: one BACKREF window per pipe), both in the order the
-// reference's single event thread would have served them.
+// reference's single event thread would have served them.  The encoder side is
+// two halves the codec layer shares (xcg_pipe_step.h, xcg_codec.cpp): the
+// encode of all frames with the pipes' state changes, and the wire's emission.
 #include <stdint.h>
 #include <string.h>
 
@@ -32,6 +34,7 @@
 
 #include "../../include/xcgpu.h"
 #include "xcg_args.h"
+#include "xcg_pipe_step.h"
 
 namespace {
 
@@ -436,10 +439,23 @@ void xcg_pipe_destroy(xcg_pipe* p) {
   delete p;
 }
 
-int xcg_pipe_encoder_consume_many(xcg_pipe* const* pipes, const uint8_t* const* data, const uint64_t* len,
-                                  uint32_t n, xcg_pipe_out* out) {
-  if (n == 0) return XCG_OK;
+}  // extern "C"
+
+// The two halves of xcg_pipe_encoder_consume_many (xcg_pipe_step.h).
+namespace xcg {
+namespace pipe {
+
+int encode_check(xcg_pipe* const* pipes, const uint8_t* const* data, const uint64_t* len, uint32_t n) {
   if (!pipes || !data || !len) return XCG_EINVAL;
+  for (uint32_t k = 0; k < n; ++k) {
+    const xcg_pipe* p = pipes[k];
+    if (!p || p->enc != pipes[0]->enc || p->encoder_sent_eos || (len[k] && !data[k])) return XCG_EINVAL;
+  }
+  return XCG_OK;
+}
+
+int encode_step(xcg_pipe* const* pipes, const uint8_t* const* data, const uint64_t* len, uint32_t n, bool on_device,
+                Encoded* e) {
   xcg_ctx* enc = pipes[0]->enc;
   // Frames of every pipe's input, in order: <= MAX_FRAME / 2 bytes each
   // (:585-600), so a frame's encoding never exceeds MAX_FRAME.
@@ -447,28 +463,33 @@ int xcg_pipe_encoder_consume_many(xcg_pipe* const* pipes, const uint8_t* const* 
   std::vector<Frame> frames;
   std::vector<uint64_t> base(n);
   uint64_t total = 0;
+  e->first.assign(n + 1, 0);
   for (uint32_t k = 0; k < n; ++k) {
-    xcg_pipe* p = pipes[k];
-    if (!p || p->enc != enc || p->encoder_sent_eos || (len[k] && !data[k])) return XCG_EINVAL;
     base[k] = total;
+    e->first[k] = (uint32_t)frames.size();
     for (uint64_t a = 0; a < len[k]; a += MAX_FRAME / 2)
       frames.push_back({k, total + a, (uint32_t)std::min<uint64_t>(MAX_FRAME / 2, len[k] - a)});
     total += len[k];
   }
+  e->first[n] = (uint32_t)frames.size();
   std::vector<uint8_t> in(total ? total : 1);
   for (uint32_t k = 0; k < n; ++k)
     if (len[k]) memcpy(in.data() + base[k], data[k], len[k]);
   const uint32_t nf = (uint32_t)frames.size();
-  std::vector<uint64_t> off(nf), oo(nf), ol(nf);
+  std::vector<uint64_t> off(nf);
   std::vector<uint32_t> fl(nf);
+  e->enc_off.assign(nf, 0);
+  e->enc_len.assign(nf, 0);
   uint64_t cap = 0;
   for (uint32_t f = 0; f < nf; ++f) {
     off[f] = frames[f].in_off;
     fl[f] = frames[f].len;
-    oo[f] = cap;
+    e->enc_off[f] = cap;
     cap += xcg_encode_bound(frames[f].len);
   }
-  std::vector<uint8_t> enc_out(cap ? cap : 1);
+  e->enc.clear();
+  e->d_enc = nullptr;
+  if (!on_device) e->enc.resize(cap ? cap : 1);
   // one GPU batch: successive encode() calls of one XCodecEncoder cache, and
   // each call's refmap as (hash, input offset) rows in std::map order.  The
   // window at a REF's offset equals the segment the REF names (find_reference
@@ -480,40 +501,82 @@ int xcg_pipe_encoder_consume_many(xcg_pipe* const* pipes, const uint8_t* const* 
   std::vector<uint64_t> rh((size_t)nf * XCG_REFMAP_MAX);
   std::vector<uint32_t> rp((size_t)nf * XCG_REFMAP_MAX), nref(nf);
   if (nf) {
-    const int rc = xcg_encode_host_refmap(enc, XCG_SEM_STREAM, in.data(), total, off.data(), fl.data(), nf,
-                                          enc_out.data(), enc_out.size(), oo.data(), ol.data(), rh.data(), rp.data(),
-                                          XCG_REFMAP_MAX, nref.data());
+    const int rc =
+        on_device ? xcg_encode_host_refmap_device(enc, XCG_SEM_STREAM, in.data(), total, off.data(), fl.data(), nf, cap,
+                                                  e->enc_off.data(), e->enc_len.data(), rh.data(), rp.data(),
+                                                  XCG_REFMAP_MAX, nref.data(), &e->d_enc)
+                  : xcg_encode_host_refmap(enc, XCG_SEM_STREAM, in.data(), total, off.data(), fl.data(), nf,
+                                           e->enc.data(), e->enc.size(), e->enc_off.data(), e->enc_len.data(),
+                                           rh.data(), rp.data(), XCG_REFMAP_MAX, nref.data());
     if (rc != XCG_OK) return rc;
+    for (uint32_t f = 0; f < nf; ++f)
+      for (uint32_t r = 0; r < nref[f] && r < XCG_REFMAP_MAX; ++r)
+        if ((uint64_t)rp[(size_t)f * XCG_REFMAP_MAX + r] + SEG > fl[f])
+          return XCG_EHIP;                               // (never: a REF stands for 2048 input bytes)
   }
-  for (uint32_t k = 0; k < n; ++k) pipes[k]->begin();
+  e->hello.assign(n, 0);
+  e->eos.assign(n, 0);
   uint32_t f = 0;
   for (uint32_t k = 0; k < n; ++k) {
     xcg_pipe* p = pipes[k];
+    p->begin();
     if (!p->encoder) {                                   // <HELLO> (:557-573)
-      p->to_peer.push_back(OP_HELLO);
-      p->to_peer.push_back((uint8_t)UUID_LEN);
-      p->to_peer.insert(p->to_peer.end(), p->uuid, p->uuid + UUID_LEN);
+      e->hello[k] = 1;
       p->encoder = true;
     }
     if (len[k] == 0) {                                   // <EOS> (:632-636)
-      p->to_peer.push_back(OP_EOS);
+      e->eos[k] = 1;
       p->encoder_sent_eos = true;
     }
     for (; f < nf && frames[f].pipe == k; ++f) {
       std::unordered_map<uint64_t, std::vector<uint8_t>> rm;
       const uint8_t* fin = in.data() + off[f];
-      for (uint32_t e = 0; e < nref[f] && e < XCG_REFMAP_MAX; ++e) {
-        const uint32_t at = rp[(size_t)f * XCG_REFMAP_MAX + e];
-        if ((uint64_t)at + SEG > fl[f]) return XCG_EHIP;     // (never: a REF stands for 2048 input bytes)
-        rm.emplace(rh[(size_t)f * XCG_REFMAP_MAX + e], std::vector<uint8_t>(fin + at, fin + at + SEG));
+      for (uint32_t r = 0; r < nref[f] && r < XCG_REFMAP_MAX; ++r) {
+        const uint32_t at = rp[(size_t)f * XCG_REFMAP_MAX + r];
+        rm.emplace(rh[(size_t)f * XCG_REFMAP_MAX + r], std::vector<uint8_t>(fin + at, fin + at + SEG));
       }
       p->ref_frames.push_back(std::move(rm));
-      p->to_peer.push_back(OP_FRAME);                    // (:620-628)
-      put_be32(p->to_peer, (uint32_t)ol[f]);
-      p->to_peer.insert(p->to_peer.end(), enc_out.begin() + (ptrdiff_t)oo[f],
-                        enc_out.begin() + (ptrdiff_t)(oo[f] + ol[f]));
     }
-    if (out) p->finish(out + k);
+  }
+  return XCG_OK;
+}
+
+void emit_wire(xcg_pipe* p, const Encoded& e, uint32_t k) {
+  if (e.hello[k]) {
+    p->to_peer.push_back(OP_HELLO);
+    p->to_peer.push_back((uint8_t)UUID_LEN);
+    p->to_peer.insert(p->to_peer.end(), p->uuid, p->uuid + UUID_LEN);
+  }
+  if (e.eos[k]) p->to_peer.push_back(OP_EOS);
+  for (uint32_t f = e.first[k]; f < e.first[k + 1]; ++f) {
+    p->to_peer.push_back(OP_FRAME);                      // (:620-628)
+    put_be32(p->to_peer, (uint32_t)e.enc_len[f]);
+    p->to_peer.insert(p->to_peer.end(), e.enc.begin() + (ptrdiff_t)e.enc_off[f],
+                      e.enc.begin() + (ptrdiff_t)(e.enc_off[f] + e.enc_len[f]));
+  }
+}
+
+const uint8_t* uuid_of(const xcg_pipe* p) { return p->uuid; }
+bool sent_eos(const xcg_pipe* p) { return p->encoder_sent_eos; }
+xcg_ctx* encoder_ctx(const xcg_pipe* p) { return p->enc; }
+void outputs(const xcg_pipe* p, xcg_pipe_out* o) { p->finish(o); }
+
+}  // namespace pipe
+}  // namespace xcg
+
+extern "C" {
+
+int xcg_pipe_encoder_consume_many(xcg_pipe* const* pipes, const uint8_t* const* data, const uint64_t* len,
+                                  uint32_t n, xcg_pipe_out* out) {
+  if (n == 0) return XCG_OK;
+  int rc = xcg::pipe::encode_check(pipes, data, len, n);
+  if (rc != XCG_OK) return rc;
+  xcg::pipe::Encoded e;
+  rc = xcg::pipe::encode_step(pipes, data, len, n, false, &e);
+  if (rc != XCG_OK) return rc;
+  for (uint32_t k = 0; k < n; ++k) {
+    xcg::pipe::emit_wire(pipes[k], e, k);
+    if (out) pipes[k]->finish(out + k);
   }
   return XCG_OK;
 }

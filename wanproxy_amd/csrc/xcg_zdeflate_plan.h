@@ -31,7 +31,7 @@ inline int check_calls(uint32_t nstreams, const uint32_t* h_stream, const uint64
                        uint32_t n) {
   std::vector<uint8_t> seen(nstreams, 0);
   for (uint32_t i = 0; i < n; i++) {
-    if (h_stream[i] >= nstreams || seen[h_stream[i]] || (h_out_off[i] & 3) || h_len[i] > (1u << 24))
+    if (h_stream[i] >= nstreams || seen[h_stream[i]] || (h_out_off[i] & 3) || h_len[i] > MAX_CALL_LEN)
       return XCG_EINVAL;
     seen[h_stream[i]] = 1;
   }

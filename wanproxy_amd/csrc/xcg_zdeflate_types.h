@@ -22,6 +22,10 @@ constexpr int XPAD = 272;                                  // zeroed bytes after
 constexpr int TAB_WORDS = L_CODES + D_CODES + BL_CODES;    // per block: code | len << 16
 constexpr int DMAX = 264;            // >= MIN_LOOKAHEAD - 1: positions a stopped flush call can leave
 constexpr uint32_t PIPE_CHUNK = 65536;   // DeflatePipe's output buffer (DEFLATE_CHUNK_SIZE, deflate_pipe.cc:34)
+// The most bytes one consume() may bring: of xcg_zdeflate_batch (check_calls, xcg_zdeflate_plan.h), and of the
+// receiving stage's xcg_zinflate_batch (xcg_inflate.hip).  Callers that refuse up front (xcg_codec.cpp) read these.
+constexpr uint32_t MAX_CALL_LEN = 1u << 24;
+constexpr uint32_t INFLATE_MAX_CALL_LEN = 1u << 26;
 
 struct ZState {          // one DeflatePipe's z_stream, reduced to what the output depends on
   uint64_t total;        // bytes consumed

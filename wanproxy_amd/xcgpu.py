@@ -198,6 +198,31 @@ def lib():
     L.xcg_pipe_decoder_consume.restype = C.c_int
     L.xcg_pipe_pending_frames.argtypes = [vp]
     L.xcg_pipe_pending_frames.restype = C.c_uint32
+    if hasattr(L, 'xcg_codec_create'):   # (an XCGPU_LIB build from before the codec layer: calling them raises)
+        many = [C.POINTER(C.c_void_p), C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(_PipeOut),
+                C.POINTER(C.c_int)]
+        L.xcg_codec_create.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.xcg_codec_create.restype = C.c_int
+        L.xcg_codec_destroy.argtypes = [vp]
+        L.xcg_codec_destroy.restype = None
+        L.xcg_codec_pipe_create.argtypes = [vp, C.c_char_p, C.POINTER(C.c_void_p)]
+        L.xcg_codec_pipe_create.restype = C.c_int
+        L.xcg_codec_pipe_destroy.argtypes = [vp]
+        L.xcg_codec_pipe_destroy.restype = None
+        L.xcg_codec_pipe_pair.argtypes = [vp]
+        L.xcg_codec_pipe_pair.restype = vp
+        L.xcg_codec_send_many.argtypes = many
+        L.xcg_codec_send_many.restype = C.c_int
+        L.xcg_codec_receive_many.argtypes = many
+        L.xcg_codec_receive_many.restype = C.c_int
+        L.xcg_codec_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.xcg_codec_stats.restype = C.c_int
+        L.xcg_debug_set_codec_fused.argtypes = [C.c_int]
+        L.xcg_debug_set_codec_fused.restype = C.c_int
+        L.xcg_codec_debug_counts.argtypes = [C.POINTER(C.c_uint64)]
+        L.xcg_codec_debug_counts.restype = None
+        L.xcg_gather_pieces.argtypes = [vp, u8p, u64p, u64p, u32p, C.c_uint32, C.c_uint32, u8p, vp]
+        L.xcg_gather_pieces.restype = C.c_int
     L.xcg_debug_set_stream_seed.argtypes = [C.c_int]
     L.xcg_debug_set_stream_seed.restype = C.c_int
     L.xcg_debug_stream_kernel_timing.argtypes = [C.c_int]
@@ -1035,6 +1060,129 @@ class PipePair:
 
     def pending_frames(self) -> int:
         return int(lib().xcg_pipe_pending_frames(self.h))
+
+
+class Codec:
+    """One WANProxyCodec (wanproxy.conf: `codec XCodec` + `compressor zlib` /
+    `compressor_level N`) over xcg_codec_*: `enc` the codec's encoder context;
+    `dec` the decoder context, or with connect=True the context its pipes'
+    decoder contexts connect from at <HELLO>; level 0-9, or -1 for no
+    compressor; at most `max_pipes` pipes alive at a time."""
+
+    def __init__(self, enc: Context, dec: Context, level: int = 6, max_pipes: int = 64, connect: bool = False):
+        self.enc, self.dec, self.level = enc, dec, level
+        h = C.c_void_p()
+        _check(lib().xcg_codec_create(enc.h, dec.h, int(connect), level, max_pipes, C.byref(h)))
+        self.h = h
+
+    def pipe(self, uuid: bytes) -> 'CodecPipe':
+        return CodecPipe(self, uuid)
+
+    def stats(self):
+        """PipeByteCount's counters: (local bytes in, bytes to the peer after
+        deflate, bytes from the peer before inflate, bytes to the local side)."""
+        st = (C.c_uint64 * 4)()
+        _check(lib().xcg_codec_stats(self.h, st))
+        return tuple(int(x) for x in st)
+
+    def close(self):
+        if getattr(self, 'h', None):
+            lib().xcg_codec_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def set_codec_fused(on: bool) -> bool:
+    """xcg_debug_set_codec_fused: the send path that keeps the wire on the
+    device (True) or the host composition (False, the default); returns the
+    previous setting."""
+    return bool(lib().xcg_debug_set_codec_fused(int(bool(on))))
+
+
+def codec_debug_counts():
+    """(fused send batches, host-composed send batches, inflate batches,
+    decode batches) the codec layer has made in this process."""
+    st = (C.c_uint64 * 4)()
+    lib().xcg_codec_debug_counts(st)
+    return tuple(int(x) for x in st)
+
+
+class CodecPipe:
+    """One side of a WANProxyCodecPipePair on a Codec: send(data) -> bytes for
+    the peer (b'' = the local side closed); receive(data) -> (to_peer,
+    to_local, local_eos, peer_eos) (b'' = the peer closed).  Close the pipes
+    before their codec."""
+
+    def __init__(self, codec: Codec, uuid: bytes):
+        self.codec = codec
+        h = C.c_void_p()
+        _check(lib().xcg_codec_pipe_create(codec.h, uuid, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, 'h', None):
+            lib().xcg_codec_pipe_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def pending_frames(self) -> int:
+        return int(lib().xcg_pipe_pending_frames(lib().xcg_codec_pipe_pair(self.h)))
+
+    def decoder_ctx(self):
+        return lib().xcg_pipe_decoder_ctx(lib().xcg_codec_pipe_pair(self.h))
+
+    @staticmethod
+    def _many(fn, pipes, datas):
+        n = len(pipes)
+        hs = (C.c_void_p * n)(*[p.h.value for p in pipes])
+        ds = (C.c_char_p * n)(*datas)
+        ls = (C.c_uint64 * n)(*[len(d) for d in datas])
+        outs = (_PipeOut * n)()
+        rcs = (C.c_int * n)(*([1] * n))                  # (1: not reached)
+        rc = fn(hs, ds, ls, n, outs, rcs)
+        if rc != 0 and (rc not in list(rcs) or 1 in list(rcs)):
+            _check(rc)                                   # refused, or an engine failure
+        res = []
+        for k, o in enumerate(outs):
+            if rcs[k] != 0:
+                res.append(XCGError(f'xcgpu: {lib().xcg_strerror(rcs[k]).decode()} ({rcs[k]})'))
+            else:
+                res.append((o.peer(), o.local(), bool(o.local_eos), bool(o.peer_eos)))
+        return res
+
+    @staticmethod
+    def send_many(pipes, datas):
+        """xcg_codec_send_many: per pipe (to_peer, b'', False, False), or the
+        XCGError of a pipe that has failed; refused calls raise."""
+        return CodecPipe._many(lib().xcg_codec_send_many, pipes, datas)
+
+    @staticmethod
+    def receive_many(pipes, datas):
+        """xcg_codec_receive_many: per pipe (to_peer, to_local, local_eos,
+        peer_eos), or the XCGError (XCG_EPROTO) of that pipe."""
+        return CodecPipe._many(lib().xcg_codec_receive_many, pipes, datas)
+
+    def send(self, data: bytes) -> bytes:
+        r = CodecPipe.send_many([self], [data])[0]
+        if isinstance(r, XCGError):
+            raise r
+        return r[0]
+
+    def receive(self, data: bytes):
+        r = CodecPipe.receive_many([self], [data])[0]
+        if isinstance(r, XCGError):
+            raise r
+        return r
 
 
 def ctx_connect(parent: Context, uuid: bytes):
