@@ -112,10 +112,12 @@ int xcg_ctx_create_ex(int device, uint32_t flags, uint64_t cache_segments, xcg_c
  * cache.  XCG_ENOTSUP (never a different result): an encode chunk, or a decode
  * call, whose own enters + persistent-entry lookups exceed the limit (encode
  * batches are cut into sub-batches that fit); XCG_SEM_INDEPENDENT with chunks of
- * more than limit * 2048 bytes; BACKREF ops in a decode on a bounded cache; a
+ * more than limit * 2048 bytes; a
  * decode batch in which any two EXTRACTs of one hash differ in bytes (name
  * reuse), or with EXTRACTs of one hash on both sides of its stop point (decode
- * it in smaller batches). */
+ * it in smaller batches).  BACKREF ops decode against the window whatever the
+ * cache has done with the slot's hash; they make no lookup, so they do not
+ * count towards the limit of a call. */
 int xcg_ctx_create_bounded(int device, uint32_t flags, uint64_t memory_cache_limit_bytes, xcg_ctx **out);
 /* A context whose persistent cache is wanproxy.conf's XCodecCachePair
  * (xcodec/xcodec_cache.h:140-237, programs/wanproxy/wanproxy.conf:8-26): a
@@ -132,9 +134,10 @@ int xcg_ctx_create_bounded(int device, uint32_t flags, uint64_t memory_cache_lim
  * with XCG_FLAG_OOB / XCG_FLAG_NULLCACHE, or a volume without one index
  * block).  XCG_ENOTSUP (never a different result): a decode batch in which a
  * hash it EXTRACTed leaves both levels before a later op names it (decode it
- * in smaller batches), BACKREF ops, name reuse inside a decode batch or
+ * in smaller batches), name reuse inside a decode batch or
  * EXTRACTs of one hash on both sides of its stop point (as on a bounded
- * context).  Decode chunks of a bounded or pair
+ * context).  BACKREF ops decode as on a bounded context: a slot keeps its bytes
+ * when its hash leaves a level, or both.  Decode chunks of a bounded or pair
  * context are < 2 MiB each (XCG_EINVAL). */
 int xcg_ctx_create_pair(int device, uint32_t flags, uint64_t memory_cache_limit_bytes, uint64_t disk_bytes,
                         xcg_ctx **out);

@@ -136,7 +136,7 @@ int decode_windows_impl(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_chun
     if (windows[w]->device != c->device) return XCG_EINVAL;
   for (uint32_t i = 0; i < n; ++i)
     if (h_chunk_window[i] >= n_windows) return XCG_EINVAL;
-  if (c->bounded || c->pair) return XCG_ENOTSUP;     // (their classification refuses BACKREFs; serial calls serve them)
+  if (c->bounded || c->pair) return XCG_ENOTSUP;     // (their classification caps at one window's BACKREF stop; serial calls serve them)
   // the plan, in the pinned block: views | chunk -> window | order | first
   const size_t nw = n_windows;
   const size_t o_cw = sizeof(xcg::WinView) * nw, o_ord = o_cw + 4ull * n, o_first = o_ord + 4ull * n,

@@ -636,10 +636,20 @@ xcg::DecParams dec_params(const XcgDecodeArgs* a) {
   }
   return p;
 }
+
+// The one-window record pass over every declare and the BACKREF check, as the
+// classified path launches them ahead of its classification.  Defined behind
+// xcg_launch_decode: the kernels are instantiated, and so laid out in the code
+// object, in the order of their first use, and the paths that launch what they
+// launched keep their kernels where they were.
+void dec_launch_records(const xcg::DecParams& p, uint64_t ndecl, hipStream_t stream);
+void dec_launch_brefcheck(const xcg::DecParams& p, hipStream_t stream);
 }  // namespace
 
 // The passes of the header comment in order: scan and declare numbering (one
-// readback), duplicate EXTRACTs, (bounded / pair) classification, refcheck and
+// readback), duplicate EXTRACTs, (bounded / pair) classification -- behind the
+// declare records and the BACKREF check when the batch holds BACKREFs, which
+// the other contexts run after it --, refcheck and
 // sizing (the second readback), (name reuse) the occurrence sort, emit, window
 // update, commit.
 // Returns 0, XCG_RC_OVERFLOW (output too small), XCG_RC_NOTSUP or XCG_RC_HIP.  Outputs: total decoded bytes, the
@@ -689,14 +699,26 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
   // Bounded cache or pair: classify every op against the eviction times until
   // they agree (xcg_decode_bounded.hip); the passes below then see the cache as
   // it evolves.
+  // BACKREFs there: the first one to an empty slot caps the classification (it
+  // follows from the declares' hashes and the window alone, so the check runs
+  // first, on records whose REF sources are made again once p.ptime stands).
   DecClassified K;
+  uint4* dfull = nullptr;
   if (classified) {
-    if (nbref > 0) return XCG_RC_NOTSUP;             // (BACKREF stop points are not modelled there)
+    if (nbref > 0) {
+      if (ndecl > 0) {
+        if (!dfull_tmp.alloc(&dfull, 16ull * ndecl)) return XCG_RC_HIP;
+        p.D = dfull;
+        p.D_lo = 0;
+        p.D_tail = false;
+        dec_launch_records(p, ndecl, stream);
+      }
+      dec_launch_brefcheck(p, stream);
+    }
     const int krc = dec_classify(a, p, ndecl, cls_tmp, &K, stream);
     if (krc) return krc;
-  }
-  uint4* dfull = nullptr;
-  if (nbref > 0 && ndecl > 0) {
+    if (dfull) dec_launch_records(p, ndecl, stream);
+  } else if (nbref > 0 && ndecl > 0) {
     // BACKREFs present: records of every declare (rare; never made by XCodecEncoder)
     if (!dfull_tmp.alloc(&dfull, 16ull * ndecl)) return XCG_RC_HIP;
     p.D = dfull;
@@ -707,7 +729,7 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
   }
   DecTimer seg2(stream, &g_dt_step);
   hipLaunchKernelGGL(decode_refcheck_kernel, grid, block, 0, stream, p);
-  if (nbref > 0) {
+  if (nbref > 0 && !classified) {
     if (a->wins) hipLaunchKernelGGL(decode_brefcheck_kernel<true>, grid, block, 0, stream, p);
     else hipLaunchKernelGGL(decode_brefcheck_kernel<false>, grid, block, 0, stream, p);
   }
@@ -816,3 +838,12 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
   seg3.end();
   return hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
 }
+
+namespace {
+void dec_launch_records(const xcg::DecParams& p, uint64_t ndecl, hipStream_t stream) {
+  hipLaunchKernelGGL(xcg::decl_record_kernel<false>, dim3((p.n + 3) / 4), dim3(256), 0, stream, p, ndecl);
+}
+void dec_launch_brefcheck(const xcg::DecParams& p, hipStream_t stream) {
+  hipLaunchKernelGGL(xcg::decode_brefcheck_kernel<false>, dim3((p.n + 3) / 4), dim3(256), 0, stream, p);
+}
+}  // namespace

@@ -46,7 +46,8 @@ struct DecParams {
   uint64_t* block_pos;         // min stream position of an unresolvable REF (atomicMin)
   int32_t* status;             // bit 9: EXTRACT name reuse inside the batch
   // ---- BACKREF window
-  uint64_t* berr_pos;          // min stream position of a BACKREF to an empty slot (atomicMin)
+  uint64_t* berr_pos;          // min stream position of a BACKREF to an empty slot (atomicMin); on a bounded or
+                               //   pair context also the classification's cap: ops behind it have no cache effect
   uint64_t* n_decl;            // scan: declares (EXTRACT + REF) per chunk
   uint64_t* n_bref;            // scan: BACKREFs per chunk
   const uint64_t* decl_base;   // exclusive scan of n_decl: batch index of the chunk's first declare
@@ -418,7 +419,9 @@ struct DecClassified {
 // Lists the ops (ndecl of them: the scan's declare count) and classifies them
 // until the eviction / departure times the classification used are the ones
 // it leaves (at most 64 passes: XCG_RC_OVERFLOW).  `tmp` owns the temporary K
-// points into; p.ptime is set for the passes that follow.
+// points into; p.ptime is set for the passes that follow.  *p.berr_pos is the
+// cap: with BACKREFs in the batch decode_brefcheck_kernel has run before this,
+// and the passes move only the unknown-REF stop in front of it.
 int dec_classify(const XcgDecodeArgs* a, DecParams& p, uint64_t ndecl, StreamTemp& tmp, DecClassified* K,
                  hipStream_t stream);
 // Before anything is emitted: dec_precheck_kernel (status bit 9).

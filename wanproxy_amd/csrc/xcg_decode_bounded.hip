@@ -54,6 +54,13 @@ __global__ __launch_bounds__(256) void dec_ops_kernel(DecParams prm, uint4* raw)
 // not at the stop.  An EXTRACT whose cached bytes differ is a REPLACE (op
 // offset | 1 << 31, GHIT): it takes a declaration row like an ENTER (the new
 // bytes' source), numbered with the ENTERs in op order.
+//
+// The cap (*prm.berr_pos: the first BACKREF to an empty slot, found before the
+// passes; a BACKREF makes no lookup, so no pass moves it): decode() returns
+// false there (:172-176) and looks at nothing behind it -- no skim -- so while
+// no unknown REF stands in front of it, every op behind it is GMISS and an
+// unknown REF there is not one.  With the unknown-REF stop in front, the skim
+// runs on over the BACKREFs (:261-266) and the cap means nothing.
 template <bool PAIR>
 __global__ __launch_bounds__(256) void dec_classify_kernel(DecParams prm, const uint4* raw, uint4* ev, uint32_t* nev,
                                                            uint4* drow, uint32_t* ndecl, uint32_t maxd,
@@ -64,6 +71,8 @@ __global__ __launch_bounds__(256) void dec_classify_kernel(DecParams prm, const 
   const uint32_t cnt = (uint32_t)prm.n_decl[c];
   const uint64_t base = prm.decl_base[c];
   const uint64_t tb = blockp == ~0ull ? ~0ull : ((blockp >> 32 << 21) | (uint32_t)blockp);
+  const uint64_t cap = readfirst64(*prm.berr_pos);
+  const bool capped = cap < blockp;                   // the error stop comes first
   const uint8_t* x = prm.in + prm.chunk_off[c];
   uint32_t nd = 0;
   bool chg = false;
@@ -74,7 +83,7 @@ __global__ __launch_bounds__(256) void dec_classify_kernel(DecParams prm, const 
     const uint64_t here = spos(c, r.z), t = ((uint64_t)c << 21) | r.z;
     uint32_t kind = EV_GMISS, ref = 0, zflag = 0;
     bool enter = false;
-    if (valid) {
+    if (valid && !(capped && here > cap)) {
       const uint64_t e = tab_lookup_t(prm.x, r.x, r.y);
       if (here <= blockp) {                           // (the op at the stop point is looked at again)
         if (e != ~0ull && e < here) {

@@ -17,7 +17,8 @@ namespace xcg {
 struct DecScratch {
   uint64_t total_out;    // exclusive scan of the decoded lengths: the batch's output bytes
   uint64_t block_pos;    // min stream position of an unresolvable REF (~0: none)
-  uint64_t berr_pos;     // min stream position of a BACKREF to an empty slot (~0: none)
+  uint64_t berr_pos;     // min stream position of a BACKREF to an empty slot (~0: none); bounded and pair
+                         //   contexts: written before the classify passes, which read it as their cap
   uint64_t dup_minus1;   // duplicate EXTRACTs listed, minus one (starts at ~0)
   uint64_t n_decl;       // declares of the batch
   uint64_t n_bref;       // BACKREFs of the batch

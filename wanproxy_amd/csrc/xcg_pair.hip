@@ -1364,9 +1364,10 @@ int pair_commit(XcgPairState* P, const PairGpu& G, hipStream_t st) {
   hipLaunchKernelGGL(pr_notocc_kernel, dim3(grid_for(P->C + 1)), dim3(256), 0, st, (const uint32_t*)P->occ, P->C,
                      P->ofl);
   if (scan_u32(P, P->ofl, P->ofr, (uint64_t)P->C + 1, st)) return XCG_RC_HIP;
+  // (before pr_free_kernel: a replaced resident's slot is freed there, and its disk link with it)
+  if (d.dec) hipLaunchKernelGGL(pr_remove_kernel, dim3(grid_for(np)), dim3(256), 0, st, d, dend);
   hipLaunchKernelGGL(pr_free_kernel, dim3(grid_for(P->C)), dim3(256), 0, st, d, (const uint32_t*)P->ofr);
   hipLaunchKernelGGL(pr_place_kernel, dim3(grid_for(np)), dim3(256), 0, st, d, dend);
-  if (d.dec) hipLaunchKernelGGL(pr_remove_kernel, dim3(grid_for(np)), dim3(256), 0, st, d, dend);
   hipLaunchKernelGGL(pr_append_kernel, dim3(grid_for(np)), dim3(256), 0, st, d, dend);
   if (hipMemcpyAsync(P->h_small, P->r1 + np, 4, hipMemcpyDeviceToHost, st) != hipSuccess || read_cnt(P, st))
     return XCG_RC_HIP;
