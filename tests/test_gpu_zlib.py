@@ -433,32 +433,15 @@ def _dyn_header_stream(syms, nlen=257, ndist=1):
     """A zlib stream whose one dynamic block header codes the code-length
     symbols `syms` [(symbol, extra value)] with a 2-bit code over {0, 8, 16,
     18} (RFC 1951 3.2.7), nothing after it."""
-    bits = []
-
-    def put(v, n):                      # LSB first
-        bits.extend((v >> i) & 1 for i in range(n))
-
-    def put_code(c, n):                 # Huffman codes MSB first
-        bits.extend((c >> (n - 1 - i)) & 1 for i in range(n))
-    put(1, 1)
-    put(2, 2)
-    put(nlen - 257, 5)
-    put(ndist - 1, 5)
-    order = [16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15]
-    lens = {0: 2, 8: 2, 16: 2, 18: 2}
-    put(len(order) - 4, 4)
-    for sym in order:
-        put(lens.get(sym, 0), 3)
-    code = {0: 0, 8: 1, 16: 2, 18: 3}
-    for sym, x in syms:
-        put_code(code[sym], 2)
-        if sym == 16:
-            put(x, 2)
-        elif sym == 18:
-            put(x, 7)
-    bits.extend([0] * (-len(bits) % 8))
-    body = bytes(sum(bits[i + k] << k for k in range(8)) for i in range(0, len(bits), 8))
-    return bytes([0x78, 0x9c]) + body + bytes(8)
+    from tests.deflate_writer import DeflateWriter
+    w = DeflateWriter()
+    w.zlib_header()
+    w.block_header(True, 2)
+    cl = [0] * 19
+    for sym in (0, 8, 16, 18):
+        cl[sym] = 2
+    w.dynamic_header([], [], nlen=nlen, ndist=ndist, cl_lens=cl, ncl=19, coding=syms)
+    return w.getvalue() + bytes(8)
 
 
 def test_inflate_dynamic_header_errors_both_kernels():

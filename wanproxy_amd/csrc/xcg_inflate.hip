@@ -155,13 +155,16 @@ __device__ __forceinline__ void wsync() {
   }
 }
 
-// Canonical decoder from code lengths (inflate_table's rules: over-subscribed
-// sets are errors, incomplete ones too unless the only code has length 1).
+// Canonical decoder from code lengths.  inflate_table's rules: an
+// over-subscribed set is an error; an empty set is accepted (using it is the
+// error: decode() finds no code); an incomplete set is an error unless its
+// longest code has one bit.  The code-length code (CL) has no such exception,
+// and an empty one returns false too: the caller decides what that means.
 // One wave, no serial loop over the symbols: per-length counts and each
 // symbol's rank among the symbols of its length come from ballots over chunks
 // of 64 symbols (canonical codes are assigned in symbol order within a
 // length), the first code and table offset of each length from the counts.
-template <int NW, class Tree>
+template <int NW, bool CL = false, class Tree>
 __device__ bool build(Lds& L, Tree& T, const uint8_t* lens, int n) {
   constexpr int PB = Tree::BITS;
   const int lane = threadIdx.x;
@@ -192,7 +195,7 @@ __device__ bool build(Lds& L, Tree& T, const uint8_t* lens, int n) {
       offs += ck;
     }
   }
-  if (ok && left > 0 && maxl != 1) ok = false;
+  if (ok && left > 0 && (CL || maxl > 1)) ok = false;
   if (lane < 16) {
     T.cnt[lane] = (uint16_t)(lane ? cnt : 0);
     L.bfirst[lane] = (uint16_t)first;
@@ -976,7 +979,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
       if (q + 16 > qend) { stall = true; break; }
       uint64_t v = R.get(q);
       uint32_t cmf = v & 0xff, flg = (v >> 8) & 0xff;
-      if (((cmf << 8) | flg) % 31 != 0 || (cmf & 15) != 8 || (cmf >> 4) > 7 || (flg & 0x20)) { mode = M_ERROR; break; }
+      if (((cmf << 8) | flg) % 31 != 0 || (cmf & 15) != 8 || (cmf >> 4) > 7) { mode = M_ERROR; break; }
+      // a preset dictionary: inflate() reads its id, then asks for one (Z_NEED_DICT, the pipe's error)
+      if (flg & 0x20) {
+        if (q + 48 > qend) stall = true;
+        else mode = M_ERROR;
+        break;
+      }
       q += 16;
       mode = M_BLOCK;
     } else if (mode == M_BLOCK) {
@@ -1017,7 +1026,16 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
           q += 3 * ncl;
         }
         wsync<NW>();
-        if (!build<NW>(L, L.ct, L.lens, 19)) { mode = M_ERROR; break; }
+        if (!build<NW, true>(L, L.ct, L.lens, 19)) {
+          // refused -- at once, unless the code is empty: inflate() then takes
+          // one bit per length from its table's filler entry, each a length 0,
+          // and misses the end-of-block code once those bits are there
+          if (!ballot(lane < 19 && L.lens[lane] != 0) && q + nlen + ndist > qend) {
+            q = q0;
+            stall = true;
+          } else mode = M_ERROR;
+          break;
+        }
         // the code-length code's 128-entry table (codes of at most 7 bits: no
         // canonical path) in one register, two entries per lane, read with
         // v_readlane instead of an LDS round trip per symbol
@@ -1195,7 +1213,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
         uint64_t v = R.get(q);
         uint32_t e = decode(L.lt, v);
         uint32_t l1 = e & 15, sym = e >> 4;
-        if (!e) { mode = (q + 15 <= qend) ? M_ERROR : mode; stall = mode != M_ERROR; break; }
+        // no such code (an end-of-block-only tree's other bit): inflate()
+        // decides with that one bit in hand
+        if (!e) { mode = (q + 1 <= qend) ? M_ERROR : mode; stall = mode != M_ERROR; break; }
         if (q + l1 > qend) { stall = true; break; }
         if (sym < 256) {
           if (pos + 1 - total0 > c.out_cap) { status = -2; break; }
@@ -1217,7 +1237,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
         uint64_t vd = R.get(qd);
         uint32_t ed = decode(L.dt, vd);
         uint32_t l2 = ed & 15, dsym = ed >> 4;
-        if (!ed) { mode = (qd + 15 <= qend) ? M_ERROR : mode; stall = mode != M_ERROR; break; }
+        // no such distance code: an empty tree or a tree of one 1-bit code
+        // (inflate() decides with one bit in hand), the fixed codes 30 / 31 (five)
+        if (!ed) { mode = (qd + (btype == 1 ? 5 : 1) <= qend) ? M_ERROR : mode; stall = mode != M_ERROR; break; }
         if (dsym > 29) { mode = M_ERROR; break; }
         uint32_t xd = DEXT[dsym];
         if (qd + l2 + xd > qend) { stall = true; break; }

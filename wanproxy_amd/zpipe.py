@@ -57,6 +57,8 @@ def _lib():
         L.xcg_zinflate_batch.restype = C.c_int
         L.xcg_debug_set_zinflate_mode.argtypes = [C.c_int]
         L.xcg_debug_set_zinflate_mode.restype = C.c_int
+        L.xcg_debug_zinflate_regions.argtypes = [vp]
+        L.xcg_debug_zinflate_regions.restype = C.c_int
         L._zd_bound = True
     return L
 
@@ -66,6 +68,15 @@ def set_inflate_mode(mode: int) -> None:
     size, 1 a wave per call, 2 a 1024-thread workgroup per call, 3 a
     256-thread workgroup per call."""
     _check(_lib().xcg_debug_set_zinflate_mode(mode))
+
+
+def inflate_region_stats():
+    """What the workgroup inflate kernels' regions did since the last call
+    (xcg_debug_zinflate_regions, which also resets the counters): (regions,
+    fixed-point passes, bytes committed, resolve rounds)."""
+    out = np.zeros(4, np.uint64)
+    _check(_lib().xcg_debug_zinflate_regions(out.ctypes.data))
+    return tuple(int(x) for x in out)
 
 
 def bound(n: int) -> int:
