@@ -653,6 +653,52 @@ int xcg_decode_call(xcg_ctx *ctx, const uint8_t *h_in, uint32_t len, uint8_t *h_
                     uint32_t unknown_cap, uint32_t *h_nunknown, uint64_t *h_extract_hash, uint32_t extract_cap,
                     uint32_t *h_nextract);
 
+/* xcg_decode_call for n calls on n DIFFERENT caches in one launch: the decode()
+ * calls a hub receives in one turn from n peers, one pipe each
+ * (XCodecCache::connect gives every peer a cache of its own,
+ * xcodec/xcodec_pipe_pair.cc:203).  Parallel arrays of n entries; call i is
+ * xcg_decode_call(ctx[i], h_in[i], len[i], h_out[i], out_cap[i], ...) on the
+ * window windows[i] (a null entry, or windows == NULL: the context's current
+ * one).  Calls on distinct unbounded caches share no decoder state, so their
+ * order does not matter: every call xcg_decode_call would decode in one launch
+ * (an unbounded context, not a null cache, len <= 1 MiB) and that is not empty
+ * goes up in ONE copy, runs as one workgroup of ONE launch, and comes back in
+ * ONE copy -- through staged device buffers of ctx[0] (its stream and its
+ * staging block; the zero-copy path stays xcg_decode_call's own).  Calls whose
+ * staging together would pass XCG_DECODE_CALL_MANY_STAGE bytes are launched
+ * in groups of consecutive calls that do not (a call that alone passes it is
+ * a group of one).
+ *
+ * Per call: h_out_len[i], h_consumed[i], h_status[i]; decode_skim's sorted set
+ * in h_unknown[i][0 .. min(h_nunknown[i], unknown_cap[i])); the EXTRACT hashes
+ * in h_extract_hash[i] (h_extract_hash, extract_cap and h_nextract may all be
+ * NULL: not wanted) as xcg_decode_call returns them; rc[i] what
+ * xcg_decode_call would have returned: XCG_EOVERFLOW with h_out_len[i] = the
+ * size needed when out_cap[i] is too small (nothing of that call is
+ * committed), XCG_EOVERFLOW on a set sticky word -- neither touches the other
+ * calls.  What the kernel declines (a BACKREF op, name reuse inside the call,
+ * more than 2048 unknown hashes, too many EXTRACTs) and what it does not take
+ * (bounded, pair and null-cache contexts, calls over 1 MiB) is served after
+ * the launch, in list order, by the batch decoder under the call's window, as
+ * xcg_decode_call serves it, with that path's rc (XCG_ENOTSUP included).
+ *
+ * The function's own return is XCG_OK unless an argument is bad or the engine
+ * fails.  XCG_EINVAL, with nothing read, written or changed: a null array other
+ * than the optional ones, a null context, a context listed twice, a window
+ * (given or a context's current one) used twice, contexts on more than one
+ * device, a window of another device, a null h_in[i] with len[i] > 0 or a null
+ * h_out[i] with out_cap[i] > 0, a null h_unknown[i] with unknown_cap[i] > 0.
+ * n == 0: XCG_OK. */
+#define XCG_DECODE_CALL_MANY_STAGE (256ull << 20)
+int xcg_decode_call_many(xcg_ctx *const *ctx, xcg_window *const *windows, const uint8_t *const *h_in,
+                         const uint32_t *len, uint8_t *const *h_out, const uint64_t *out_cap, uint32_t n,
+                         uint64_t *h_out_len, uint64_t *h_consumed, int32_t *h_status, uint64_t *const *h_unknown,
+                         const uint32_t *unknown_cap, uint32_t *h_nunknown, uint64_t *const *h_extract_hash,
+                         const uint32_t *extract_cap, uint32_t *h_nextract, int *rc);
+/* Diagnostics, process-wide: launches xcg_decode_call_many has made, calls the
+ * kernel finished in them, and calls served outside the launch. */
+void xcg_debug_decode_call_many(uint64_t out[3]);
+
 /* Pack n output slots (d_out + d_out_off[i], d_out_len[i] bytes) back to back
  * into d_packed; d_packed_off[i] receives each chunk's offset and *d_total
  * (device) the packed size.  Asynchronous on `stream`. */
@@ -719,17 +765,25 @@ int xcg_pipe_encoder_consume_many(xcg_pipe *const *pipes, const uint8_t *const *
  * rc[k] (nullable), the decoder contexts' caches and every pipe's window and
  * buffered state exactly as that loop leaves them -- with the decode() calls
  * of consecutive pipes that decode on one unbounded context made in ONE GPU
- * batch (xcg_decode_host_windows, one window per pipe).  A pipe whose bytes
- * hold a <LEARN>, a connecting pipe before its <HELLO> and a pipe on a bounded
- * or pair context are served by the serial call in their place.  A pipe that
- * fails (XCG_EPROTO) does not stop the others.  Returns the first nonzero
- * rc[k]; XCG_EINVAL before anything changes for null arguments or a pipe
- * listed twice; an engine failure at once. */
+ * batch (xcg_decode_host_windows, one window per pipe), and the decode() calls
+ * of pipes that each stand alone on an unbounded context of their own -- a
+ * hub's turn: many peers, a pipe each -- in ONE launch (xcg_decode_call_many,
+ * a workgroup per pipe; calls of at most 1 MiB of buffered frame bytes, two or
+ * more of them).  A pipe whose bytes hold a <LEARN>, a connecting pipe before
+ * its <HELLO> and a pipe on a bounded or pair context are served by the serial
+ * call in their place.  A pipe that fails (XCG_EPROTO) does not stop the
+ * others.  Returns the nonzero rc[k] of the lowest k; XCG_EINVAL before
+ * anything changes for null arguments or a pipe listed twice; an engine
+ * failure at once. */
 int xcg_pipe_decoder_consume_many(xcg_pipe *const *pipes, const uint8_t *const *data, const uint64_t *len, uint32_t n,
                                   xcg_pipe_out *out, int *rc);
-/* Diagnostics: the batched decode calls xcg_pipe_decoder_consume_many has made
- * in this process, and the chunks (one per pipe) they held. */
+/* Diagnostics: the batched decode calls (xcg_decode_host_windows)
+ * xcg_pipe_decoder_consume_many has made in this process, and the chunks (one
+ * per pipe) they held. */
 void xcg_pipe_debug_decode_many(uint64_t out[2]);
+/* Diagnostics: the xcg_decode_call_many calls xcg_pipe_decoder_consume_many has
+ * made in this process (one pipe per peer cache), and the pipes in them. */
+void xcg_pipe_debug_decode_peers(uint64_t out[2]);
 int xcg_pipe_decoder_consume(xcg_pipe *p, const uint8_t *data, uint64_t len, xcg_pipe_out *out);
 /* Frames whose REF segments the encoder still keeps for <ASK> (not yet <ADVANCE>d). */
 uint32_t xcg_pipe_pending_frames(const xcg_pipe *p);

@@ -1,13 +1,15 @@
 // Decode entry points of the C ABI declared in include/xcgpu.h: batch,
-// independent, grouped, host and call (with its zero-copy path), the BACKREF
-// windows and the phase diagnostics.
+// independent, grouped, host and call (with its zero-copy path), many calls on
+// many caches in one launch, the BACKREF windows and the phase diagnostics.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
+#include <functional>
 #include <mutex>
 #include <vector>
 
@@ -433,6 +435,24 @@ bool getenv_flag_no_zc() {
   return off;
 }
 
+// The calls xcg_decode_call and xcg_decode_call_many decode in one launch
+// (decode_small_body): an unbounded cache that is not the null cache, and an
+// input the kernel's op scratch is sized for.
+bool decode_call_fast(const xcg_ctx* c, uint32_t len) {
+  return !c->bounded && !c->pair && !(c->flags & XCG_FLAG_NULLCACHE) && len <= (1u << 20);
+}
+
+// Every other call, and a call the kernel declined: one chunk through the
+// batch decoder on the context's current window.
+int decode_call_batch(xcg_ctx* c, const uint8_t* h_in, uint32_t len, uint8_t* h_out, uint64_t out_cap,
+                      uint64_t* h_out_len, uint64_t* h_consumed, int32_t* h_status, uint64_t* h_unknown,
+                      uint32_t unknown_cap, uint32_t* h_nunknown) {
+  const uint64_t off = 0;
+  uint64_t ooff = 0;
+  return xcg_decode_host(c, h_in, len, &off, &len, 1, h_out, out_cap, &ooff, h_out_len, h_status, h_consumed,
+                         h_unknown, unknown_cap, h_nunknown);
+}
+
 // One decode() in one launch with no copies: the kernel reads the input from,
 // and writes the output and results to, coherent pinned host memory, then
 // stores the call's sequence number there; the host waits on that word (a
@@ -518,7 +538,7 @@ int xcg_decode_call(xcg_ctx* c, const uint8_t* h_in, uint32_t len, uint8_t* h_ou
   *h_nextract = XCG_NO_REFERENCES;
   if (len == 0) return XCG_OK;
   DeviceGuard g(c->device);
-  const bool fast = !c->bounded && !c->pair && !(c->flags & XCG_FLAG_NULLCACHE) && len <= (1u << 20);
+  const bool fast = decode_call_fast(c, len);
   if (fast) {
     int rc = ensure_cache(c);
     if (rc == XCG_OK && !c->cur_win) {
@@ -532,10 +552,8 @@ int xcg_decode_call(xcg_ctx* c, const uint8_t* h_in, uint32_t len, uint8_t* h_ou
                           unknown_cap, h_nunknown, h_extract_hash, extract_cap, h_nextract);
       if (rc != XCG_ENOTSUP) return rc;
       // (fallback: the batch decoder takes it; nothing was written)
-      const uint64_t off = 0;
-      uint64_t ooff = 0;
-      return xcg_decode_host(c, h_in, len, &off, &len, 1, h_out, out_cap, &ooff, h_out_len, h_status, h_consumed,
-                             h_unknown, unknown_cap, h_nunknown);
+      return decode_call_batch(c, h_in, len, h_out, out_cap, h_out_len, h_consumed, h_status, h_unknown, unknown_cap,
+                               h_nunknown);
     }
     // device: input | output | results | op lists;  host: input | output | results (one D2H brings
     // both back; the results' last word is the context's sticky word)
@@ -579,11 +597,166 @@ int xcg_decode_call(xcg_ctx* c, const uint8_t* h_in, uint32_t len, uint8_t* h_ou
     if (r2 != XCG_ENOTSUP) return r2;
     // (fallback: the batch decoder takes it; nothing was written)
   }
-  const uint64_t off = 0;
-  uint64_t ooff = 0;
-  const int rc = xcg_decode_host(c, h_in, len, &off, &len, 1, h_out, out_cap, &ooff, h_out_len, h_status, h_consumed,
-                                 h_unknown, unknown_cap, h_nunknown);
-  return rc;
+  return decode_call_batch(c, h_in, len, h_out, out_cap, h_out_len, h_consumed, h_status, h_unknown, unknown_cap,
+                           h_nunknown);
+}
+
+}  // extern "C"
+
+namespace {
+std::atomic<uint64_t> g_dcm_launches{0}, g_dcm_done{0}, g_dcm_outside{0};
+
+struct ManyCall {                  // one call of a group, as staged
+  uint32_t i;                      // its place in the caller's arrays
+  xcg_window* w;
+  size_t in_off, out_off, res_off, scr_off;   // in the up block, the down block (both), the scratch block
+  uint32_t ops_cap;
+};
+// What call i stages on the device: its record, input, output, results and op scratch.
+size_t many_call_bytes(uint32_t len, uint64_t out_cap) {
+  return align_up(xcg_small_dec_size(), 256) + align_up(len, 256) + align_up(out_cap ? out_cap : 1, 256) +
+         align_up(8ull * xcg::SD_RES_WORDS, 256) + align_up(xcg::SD_SCRATCH_PER_OP * (len / 4 + 64), 256);
+}
+}  // namespace
+
+extern "C" {
+
+int xcg_decode_call_many(xcg_ctx* const* ctx, xcg_window* const* windows, const uint8_t* const* h_in,
+                         const uint32_t* len, uint8_t* const* h_out, const uint64_t* out_cap, uint32_t n,
+                         uint64_t* h_out_len, uint64_t* h_consumed, int32_t* h_status, uint64_t* const* h_unknown,
+                         const uint32_t* unknown_cap, uint32_t* h_nunknown, uint64_t* const* h_extract_hash,
+                         const uint32_t* extract_cap, uint32_t* h_nextract, int* rc_out) {
+  if (n == 0) return XCG_OK;
+  if (!ctx || !h_in || !len || !h_out || !out_cap || !h_out_len || !h_consumed || !h_status || !h_unknown ||
+      !unknown_cap || !h_nunknown || !rc_out || (h_extract_hash && (!extract_cap || !h_nextract)))
+    return XCG_EINVAL;
+  std::vector<xcg_window*> win(n);
+  {
+    std::vector<const void*> cs, ws;
+    for (uint32_t i = 0; i < n; ++i) {
+      xcg_ctx* c = ctx[i];
+      if (!c || c->device != ctx[0]->device || (len[i] && !h_in[i]) || (out_cap[i] && !h_out[i]) ||
+          (unknown_cap[i] && !h_unknown[i]))
+        return XCG_EINVAL;
+      win[i] = windows && windows[i] ? windows[i] : c->cur_win;   // (null: the context's own, not made yet)
+      if (win[i] && win[i]->device != c->device) return XCG_EINVAL;
+      cs.push_back(c);
+      if (win[i]) ws.push_back(win[i]);
+    }
+    std::sort(cs.begin(), cs.end(), std::less<const void*>());
+    std::sort(ws.begin(), ws.end(), std::less<const void*>());
+    if (std::adjacent_find(cs.begin(), cs.end()) != cs.end() || std::adjacent_find(ws.begin(), ws.end()) != ws.end())
+      return XCG_EINVAL;
+  }
+  std::vector<uint32_t> outside;                        // calls the launch does not serve
+  std::vector<uint32_t> elig;
+  for (uint32_t i = 0; i < n; ++i) {
+    h_out_len[i] = h_consumed[i] = 0;
+    h_status[i] = 0;
+    h_nunknown[i] = 0;
+    if (h_nextract) h_nextract[i] = XCG_NO_REFERENCES;
+    rc_out[i] = XCG_OK;
+    if (len[i] == 0) continue;
+    (decode_call_fast(ctx[i], len[i]) ? elig : outside).push_back(i);
+  }
+  DeviceGuard g(ctx[0]->device);
+  const size_t recb = xcg_small_dec_size(), resb = align_up(8ull * xcg::SD_RES_WORDS, 256);
+  size_t e0 = 0;
+  while (e0 < elig.size()) {
+    // the group: consecutive eligible calls whose staging stays under the bound
+    size_t e1 = e0, bytes = 0;
+    while (e1 < elig.size()) {
+      const size_t b = many_call_bytes(len[elig[e1]], out_cap[elig[e1]]);
+      if (e1 > e0 && bytes + b > XCG_DECODE_CALL_MANY_STAGE) break;
+      bytes += b;
+      ++e1;
+    }
+    const uint32_t m = (uint32_t)(e1 - e0);
+    xcg_ctx* c0 = ctx[elig[e0]];
+    // up: records | inputs;  down: per call output | results;  then the op scratch (device only)
+    std::vector<ManyCall> mc(m);
+    size_t up = align_up(recb * m, 256), down = 0, scr = 0;
+    for (uint32_t k = 0; k < m; ++k) {
+      ManyCall& q = mc[k];
+      q.i = elig[e0 + k];
+      xcg_ctx* c = ctx[q.i];
+      int rc = ensure_cache(c);
+      if (rc == XCG_OK && !win[q.i]) {
+        if (!c->own_win) rc = window_alloc(c->device, &c->own_win);
+        c->cur_win = c->own_win;
+        win[q.i] = c->cur_win;
+      }
+      if (rc != XCG_OK) return rc;
+      q.w = win[q.i];
+      q.ops_cap = len[q.i] / 4 + 64;
+      q.in_off = up;
+      up += align_up(len[q.i], 256);
+      q.out_off = down;
+      down += align_up(out_cap[q.i] ? out_cap[q.i] : 1, 256);
+      q.res_off = down;
+      down += resb;
+      q.scr_off = scr;
+      scr += align_up(xcg::SD_SCRATCH_PER_OP * q.ops_cap, 256);
+    }
+    int rc = ensure_stage(c0, up + down + scr, up + down);
+    if (rc != XCG_OK) return rc;
+    uint8_t* dm = c0->stage_d;
+    uint8_t* hm = c0->stage_h;
+    const hipStream_t st = c0->call_st;
+    for (uint32_t k = 0; k < m; ++k) {
+      const ManyCall& q = mc[k];
+      xcg_ctx* c = ctx[q.i];
+      memcpy(hm + q.in_off, h_in[q.i], len[q.i]);
+      xcg_small_dec_fill(hm + recb * k, dm + q.in_off, len[q.i], &c->g, c->d_status, dm + up + down + q.scr_off,
+                         q.ops_cap, dm + up + q.out_off, out_cap[q.i], q.w->hash, q.w->seg, q.w->count,
+                         (uint64_t*)(dm + up + q.res_off));
+      ctx_order(c, st);                                 // behind every listed context's earlier work
+    }
+    const bool ok = hipMemcpyAsync(dm, hm, up, hipMemcpyHostToDevice, st) == hipSuccess &&
+                    xcg_launch_decode_calls(dm, m, st) == 0 &&
+                    hipMemcpyAsync(hm + up, dm + up, down, hipMemcpyDeviceToHost, st) == hipSuccess;
+    for (uint32_t k = 0; k < m; ++k) ctx_mark(ctx[mc[k].i], st);
+    if (!ok || hipStreamSynchronize(st) != hipSuccess) return XCG_EHIP;
+    // (the stream is c0's: the other contexts record their completion now, while it certainly exists)
+    for (uint32_t k = 0; k < m; ++k)
+      if (ctx[mc[k].i] != c0) ctx_flush_mark(ctx[mc[k].i]);
+    ++g_dcm_launches;
+    for (uint32_t k = 0; k < m; ++k) {
+      const ManyCall& q = mc[k];
+      const uint32_t i = q.i;
+      uint32_t ne = XCG_NO_REFERENCES;
+      const int r2 = decode_call_results(&q.w->count, (const uint64_t*)(hm + up + q.res_off), hm + up + q.out_off,
+                                         h_out[i], &h_out_len[i], &h_consumed[i], &h_status[i], h_unknown[i],
+                                         unknown_cap[i], &h_nunknown[i], h_extract_hash ? h_extract_hash[i] : nullptr,
+                                         h_extract_hash ? extract_cap[i] : 0u, &ne);
+      if (r2 == XCG_ENOTSUP) {                          // the kernel declined; nothing was written
+        outside.push_back(i);
+        continue;
+      }
+      if (h_nextract) h_nextract[i] = ne;
+      rc_out[i] = r2;
+      if (r2 == XCG_OK) ++g_dcm_done;
+    }
+    e0 = e1;
+  }
+  // in list order (pair fronts of one disk keep theirs), each on its window
+  std::sort(outside.begin(), outside.end());
+  for (const uint32_t i : outside) {
+    xcg_ctx* c = ctx[i];
+    xcg_window* const prev = c->cur_win;
+    if (windows && windows[i]) c->cur_win = windows[i];
+    rc_out[i] = decode_call_batch(c, h_in[i], len[i], h_out[i], out_cap[i], &h_out_len[i], &h_consumed[i],
+                                  &h_status[i], h_unknown[i], unknown_cap[i], &h_nunknown[i]);
+    c->cur_win = prev ? prev : c->own_win;
+    ++g_dcm_outside;
+  }
+  return XCG_OK;
+}
+
+void xcg_debug_decode_call_many(uint64_t out[3]) {
+  out[0] = g_dcm_launches;
+  out[1] = g_dcm_done;
+  out[2] = g_dcm_outside;
 }
 
 uint32_t xcg_debug_decode_phases(double* us, uint32_t n) {

@@ -438,6 +438,14 @@ extern "C" int xcg_launch_decode_small(const uint8_t* in, uint32_t len, const Xc
                                        void* scratch, uint32_t ops_cap, uint8_t* out, uint64_t out_cap,
                                        uint64_t* win_hash, uint8_t* win_seg, uint64_t win_count, uint64_t* res,
                                        uint64_t* tim, uint32_t* flag, uint32_t seq, hipStream_t stream);
+// n such calls on n distinct caches in one launch (decode_calls_kernel): the
+// host fills one record per call (xcg_small_dec_size() bytes each, 8-byte
+// aligned) into the block it copies up, then launches over the device copy.
+extern "C" uint32_t xcg_small_dec_size(void);
+extern "C" void xcg_small_dec_fill(void* rec, const uint8_t* in, uint32_t len, const XcgCacheView* g, int32_t* status,
+                                   void* scratch, uint32_t ops_cap, uint8_t* out, uint64_t out_cap,
+                                   uint64_t* win_hash, uint8_t* win_seg, uint64_t win_count, uint64_t* res);
+extern "C" int xcg_launch_decode_calls(const void* d_recs, uint32_t n, hipStream_t stream);
 
 // (xcg_ctx.hip for xcg_pipe.cpp) a connecting pipe takes and drops its registry context
 // (connect_hold: xcg_ctx_connect with the hold taken under the registry lock)

@@ -1,5 +1,6 @@
 // XCodec decoder, one decode() call in one workgroup (the batch decoder's
-// passes and helpers: xcg_decode.hip, xcg_decode_batch.h).
+// passes and helpers: xcg_decode.hip, xcg_decode_batch.h): one call a launch
+// (decode_small_kernel), or n calls on n caches a launch (decode_calls_kernel).
 //
 // XCodecDecoder::decode (xcodec/xcodec_decoder.cc:66-272) of ONE call's input
 // on an unbounded cache, as the drop-in adapter issues it (tack -d: one call
@@ -444,7 +445,68 @@ __global__ __launch_bounds__(1024) void decode_small_kernel(SmallDec a) {
   }
 }
 
+// N decode() calls on N distinct caches and windows in one launch: workgroup b
+// is the whole call calls[b].  The calls share nothing, so the blocks need no
+// order among themselves; completion is the stream's (flag and tim are null).
+// The record's address depends on blockIdx.x alone, so its loads are scalar and
+// the pointers and lengths stay in SGPRs, as decode_small_kernel's kernel
+// arguments do.
+__global__ __launch_bounds__(1024) void decode_calls_kernel(const SmallDec* __restrict__ calls, uint32_t n) {
+  if (blockIdx.x >= n) return;
+  const SmallDec a = calls[blockIdx.x];
+  decode_small_body(a);
+}
+
 }  // namespace xcg
+
+// One SmallDec record (host side): the cache view, the op scratch's three
+// arrays and the call's buffers.
+static xcg::SmallDec small_dec_of(const uint8_t* in, uint32_t len, const XcgCacheView* g, int32_t* status,
+                                  void* scratch, uint32_t ops_cap, uint8_t* out, uint64_t out_cap,
+                                  uint64_t* win_hash, uint8_t* win_seg, uint64_t win_count, uint64_t* res) {
+  using namespace xcg;
+  SmallDec a;
+  a.in = in;
+  a.len = len;
+  a.g = tab_of(*g);
+  a.pool = g->pool;
+  a.nseg = g->nseg;
+  a.seg_cap = g->seg_cap;
+  a.fs = filters_of(*g);
+  a.status = status;
+  a.ops = (uint4*)scratch;
+  a.opv = (uint64_t*)(a.ops + ops_cap);
+  a.D = (uint4*)(a.opv + ops_cap);
+  a.ops_cap = ops_cap;
+  a.out = out;
+  a.out_cap = out_cap;
+  a.win_hash = win_hash;
+  a.win_seg = win_seg;
+  a.win_count = win_count;
+  a.res = res;
+  a.tim = nullptr;
+  a.flag = nullptr;
+  a.seq = 0;
+  return a;
+}
+
+// The records of decode_calls_kernel, written by the host into the block it
+// copies up with the inputs: xcg_small_dec_size() bytes each, 8-byte aligned.
+extern "C" uint32_t xcg_small_dec_size(void) { return (uint32_t)sizeof(xcg::SmallDec); }
+extern "C" void xcg_small_dec_fill(void* rec, const uint8_t* in, uint32_t len, const XcgCacheView* g, int32_t* status,
+                                   void* scratch, uint32_t ops_cap, uint8_t* out, uint64_t out_cap,
+                                   uint64_t* win_hash, uint8_t* win_seg, uint64_t win_count, uint64_t* res) {
+  *(xcg::SmallDec*)rec = small_dec_of(in, len, g, status, scratch, ops_cap, out, out_cap, win_hash, win_seg, win_count, res);
+}
+
+// n decode() calls on n distinct unbounded caches in one launch
+// (decode_calls_kernel); d_recs: n records in device memory.
+extern "C" int xcg_launch_decode_calls(const void* d_recs, uint32_t n, hipStream_t stream) {
+  using namespace xcg;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(decode_calls_kernel, dim3(n), dim3(1024), 0, stream, (const SmallDec*)d_recs, n);
+  return hipGetLastError() == hipSuccess ? 0 : XCG_RC_HIP;
+}
 
 // One decode() call on an unbounded cache in one launch (decode_small_kernel).
 extern "C" int xcg_launch_decode_small(const uint8_t* in, uint32_t len, const XcgCacheView* g, int32_t* status,

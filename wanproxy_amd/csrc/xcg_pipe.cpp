@@ -16,7 +16,8 @@
 // an encoder context (one codec, one cache) can be encoded in one GPU batch
 // (xcg_pipe_encoder_consume_many), and pipes that share a decoder context (one
 // peer's cache) decoded in one (xcg_pipe_decoder_consume_many, over
-// xcg_decode_host_windows: one BACKREF window per pipe), both in the order the
+// xcg_decode_host_windows: one BACKREF window per pipe; pipes that each stand
+// alone on a peer's cache in one launch, xcg_decode_call_many), both in the order the
 // reference's single event thread would have served them.  The encoder side is
 // two halves the codec layer shares (xcg_pipe_step.h, xcg_codec.cpp): the
 // encode of all frames with the pipes' state changes, and the wire's emission.
@@ -389,6 +390,13 @@ bool reaches_learn(const uint8_t* b, size_t n) {
 // Diagnostics (xcg_pipe_debug_decode_many): batched decode calls made by
 // xcg_pipe_decoder_consume_many and the chunks in them, process-wide.
 std::atomic<uint64_t> g_many_calls{0}, g_many_chunks{0};
+// (xcg_pipe_debug_decode_peers): xcg_decode_call_many calls made there, one
+// pipe per peer cache, and the pipes in them.
+std::atomic<uint64_t> g_peer_calls{0}, g_peer_pipes{0};
+// Held pipes go up together from this many on; fewer take the single call.
+// (Measured: scripts/pipe_peers_time.py)
+constexpr uint32_t PEERS_MIN = 2;
+constexpr size_t PEERS_MAX_CALL = 1u << 20;              // what xcg_decode_call_many decodes in its launch
 
 // A pipe xcg_pipe_decoder_consume_many may take into a run (see there).
 bool plain(const xcg_pipe* p, const uint8_t* data, uint64_t len) {
@@ -619,7 +627,20 @@ int xcg_pipe_decoder_consume(xcg_pipe* p, const uint8_t* data, uint64_t len, xcg
 // done, the stopped pipe takes its consumed prefix and -- blocked on a REF --
 // the single call once more for decode_skim's set (that call blocks on its
 // first op: it consumes and declares nothing), and the pipes behind it are
-// the next batch.  Every other pipe, and a run of one, is the serial call.
+// the next batch.  Every other pipe is the serial call.
+//
+// A run of ONE -- a hub's turn: many peers, a pipe each -- runs its ops at once
+// and, if that leaves frame bytes to decode (no unknown hash outstanding, at
+// most 1 MiB buffered), is *held*: its decode() waits.  A held pipe decodes on
+// an unbounded context no other unfinished pipe of the call uses, its
+// decode_ops touched no cache, and pipes on distinct unbounded contexts share
+// no decoder state (cache, window and buffers are per context or per pipe), so
+// the held calls may run in any order, and together.  The held set is flushed
+// before a later pipe whose context is in it, before a connecting pipe that
+// has no context yet (it may connect to one of them) and at the end: one pipe
+// by decode_data(), PEERS_MIN or more by one xcg_decode_call_many over the
+// pipes' windows and frame buffers, whose per-call results (decode_skim's set
+// included: no second call) end in apply_decoded as the single call's do.
 int xcg_pipe_decoder_consume_many(xcg_pipe* const* pipes, const uint8_t* const* data, const uint64_t* len,
                                   uint32_t n, xcg_pipe_out* out, int* rc_out) {
   if (n == 0) return XCG_OK;
@@ -631,20 +652,118 @@ int xcg_pipe_decoder_consume_many(xcg_pipe* const* pipes, const uint8_t* const* 
     std::sort(s.begin(), s.end(), std::less<const xcg_pipe*>());
     if (std::adjacent_find(s.begin(), s.end()) != s.end()) return XCG_EINVAL;   // a pipe listed twice
   }
-  int first = XCG_OK;
+  std::vector<int> rcs(n, XCG_OK);                       // (held pipes finish out of order)
   const auto done = [&](uint32_t k, int rc) {
     if (rc_out) rc_out[k] = rc;
-    if (rc != XCG_OK && first == XCG_OK) first = rc;
+    rcs[k] = rc;
     if (out) pipes[k]->finish(out + k);
   };
   const auto serial = [&](uint32_t k) {
     done(k, xcg_pipe_decoder_consume(pipes[k], data[k], len[k], out ? out + k : nullptr));
   };
+  // The held set: pipes whose ops are done and whose decode() waits for the
+  // flush, each on a context of its own.
+  std::vector<uint32_t> held;
+  const auto is_held = [&](const xcg_ctx* c) {
+    for (const uint32_t h : held)
+      if (pipes[h]->dec == c) return true;
+    return false;
+  };
+  const auto flush = [&]() -> int {
+    const uint32_t m = (uint32_t)held.size();
+    if (m < PEERS_MIN) {                                 // the single call
+      for (const uint32_t h : held) {
+        xcg_pipe* p = pipes[h];
+        const int rc = p->decode_data();
+        p->settle(rc);
+        done(h, rc);
+      }
+      held.clear();
+      return XCG_OK;
+    }
+    constexpr uint32_t UCAP = 1u << 16;                  // (decode_data's)
+    std::vector<xcg_ctx*> cs(m);
+    std::vector<xcg_window*> ws(m);
+    std::vector<const uint8_t*> in(m);
+    std::vector<uint32_t> il(m), ucap(m, UCAP), nunk(m);
+    std::vector<uint8_t*> op(m);
+    std::vector<uint64_t> cap(m), ol(m), cons(m);
+    std::vector<uint64_t*> up(m);
+    std::vector<int32_t> st(m);
+    std::vector<int> crc(m);
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < m; ++i) {
+      const xcg_pipe* p = pipes[held[i]];
+      cs[i] = p->dec;
+      ws[i] = p->win;
+      in[i] = p->fbuf.data();
+      il[i] = (uint32_t)p->fbuf.size();
+      cap[i] = decoded_bound(in[i], il[i]) + 4096;
+      total += cap[i];
+    }
+    std::unique_ptr<uint8_t[]> dout(new uint8_t[total]);
+    std::unique_ptr<uint64_t[]> unk(new uint64_t[(size_t)m * UCAP]);   // (not filled: the calls write what they count)
+    total = 0;
+    for (uint32_t i = 0; i < m; ++i) {
+      op[i] = dout.get() + total;
+      total += cap[i];
+      up[i] = unk.get() + (size_t)i * UCAP;
+    }
+    const int brc = xcg_decode_call_many(cs.data(), ws.data(), in.data(), il.data(), op.data(), cap.data(), m,
+                                         ol.data(), cons.data(), st.data(), up.data(), ucap.data(), nunk.data(),
+                                         nullptr, nullptr, nullptr, crc.data());
+    if (brc != XCG_OK) return brc;                       // an engine failure: at once
+    ++g_peer_calls;
+    g_peer_pipes += m;
+    for (uint32_t i = 0; i < m; ++i) {
+      xcg_pipe* p = pipes[held[i]];
+      int rc = crc[i];
+      if (rc == XCG_OK) rc = p->apply_decoded(st[i], cons[i], op[i], ol[i], up[i], nunk[i]);
+      p->settle(rc);
+      done(held[i], rc);
+    }
+    held.clear();
+    return XCG_OK;
+  };
+  const auto result = [&]() {
+    for (uint32_t j = 0; j < n; ++j)
+      if (rcs[j] != XCG_OK) return rcs[j];
+    return (int)XCG_OK;
+  };
   uint32_t k = 0;
   while (k < n) {
     xcg_ctx* const ctx = pipes[k]->dec;
+    // a pipe of a held context, or one that may connect to one: the held calls first
+    if (!held.empty() && (!ctx || is_held(ctx))) {
+      const int frc = flush();
+      if (frc != XCG_OK) return frc;
+    }
     uint32_t e = k;
     while (e < n && pipes[e]->dec == ctx && plain(pipes[e], data[e], len[e])) ++e;
+    if (e - k == 1) {
+      // a run of one: its ops now; its decode() joins the held set
+      xcg_pipe* p = pipes[k];
+      p->begin();
+      if (len[k] == 0) {                                 // peer closed (:72-87)
+        if (!p->decoder_sent_eos) {
+          p->decoder_sent_eos = true;
+          p->local_eos = 1;
+        }
+        done(k++, XCG_OK);
+        continue;
+      }
+      p->dbuf.insert(p->dbuf.end(), data[k], data[k] + len[k]);
+      const int rc = p->decode_ops();
+      if (rc == XCG_OK && p->unknown.empty() && !p->fbuf.empty() && p->fbuf.size() <= PEERS_MAX_CALL) {
+        held.push_back(k++);
+        continue;
+      }
+      int rc2 = rc;
+      if (rc == XCG_OK && p->unknown.empty()) rc2 = p->decode_data();
+      p->settle(rc2);
+      done(k++, rc2);
+      continue;
+    }
     if (e - k < 2) {
       serial(k++);
       continue;
@@ -717,12 +836,19 @@ int xcg_pipe_decoder_consume_many(xcg_pipe* const* pipes, const uint8_t* const* 
     }
     k = e;
   }
-  return first;
+  const int frc = flush();
+  if (frc != XCG_OK) return frc;
+  return result();
 }
 
 void xcg_pipe_debug_decode_many(uint64_t out[2]) {
   out[0] = g_many_calls;
   out[1] = g_many_chunks;
+}
+
+void xcg_pipe_debug_decode_peers(uint64_t out[2]) {
+  out[0] = g_peer_calls;
+  out[1] = g_peer_pipes;
 }
 
 uint32_t xcg_pipe_pending_frames(const xcg_pipe* p) { return p ? (uint32_t)p->ref_frames.size() : 0u; }

@@ -196,6 +196,13 @@ def lib():
                                                     C.POINTER(C.c_int)]
         L.xcg_pipe_decoder_consume_many.restype = C.c_int
     L.xcg_pipe_decoder_consume.restype = C.c_int
+    if hasattr(L, 'xcg_decode_call_many'):
+        L.xcg_decode_call_many.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.xcg_decode_call_many.restype = C.c_int
+        L.xcg_debug_decode_call_many.argtypes = [C.POINTER(C.c_uint64)]
+        L.xcg_debug_decode_call_many.restype = None
+        L.xcg_pipe_debug_decode_peers.argtypes = [C.POINTER(C.c_uint64)]
+        L.xcg_pipe_debug_decode_peers.restype = None
     L.xcg_pipe_pending_frames.argtypes = [vp]
     L.xcg_pipe_pending_frames.restype = C.c_uint32
     if hasattr(L, 'xcg_codec_create'):   # (an XCGPU_LIB build from before the codec layer: calling them raises)
@@ -1037,8 +1044,10 @@ class PipePair:
     @staticmethod
     def decoder_consume_many(pipes, datas):
         """decoder_consume(datas[k]) of every pipe in order, the decode() calls of
-        consecutive pipes on one decoder context in one GPU batch
-        (xcg_pipe_decoder_consume_many).  One (to_peer, to_local, local_eos,
+        consecutive pipes on one decoder context in one GPU batch and those of
+        pipes that each stand alone on a context of their own (many peers, a
+        pipe each) in one launch (xcg_pipe_decoder_consume_many:
+        xcg_decode_host_windows, xcg_decode_call_many).  One (to_peer, to_local, local_eos,
         peer_eos) per pipe, or the XCGError its serial call would have raised;
         bad arguments (a pipe listed twice) and engine failures raise."""
         n = len(pipes)
@@ -1183,6 +1192,73 @@ class CodecPipe:
         if isinstance(r, XCGError):
             raise r
         return r
+
+
+def decode_call_many(calls, want_extracts: bool = True, out_lens: list = None):
+    """xcg_decode_call_many: one decode() call per entry of `calls`, each
+    (Context, Window or None, bytes[, out_cap]) on a context (and window) of its
+    own, the calls an unbounded cache decodes in one launch all in ONE launch.
+    Returns per call (rc, status, out, consumed, unknown, extract_hashes or
+    None); bad arguments (a context or window listed twice, more than one
+    device) and engine failures raise.  out_lens (a list) receives every call's
+    out_len: with rc -75 for too little room, the size that call needs."""
+    n = len(calls)
+    if n == 0:
+        _check(lib().xcg_decode_call_many(None, None, None, None, None, None, 0, None, None, None, None, None, None,
+                                          None, None, None, None))
+        return []
+    UCAP, ECAP = 1 << 16, 1024
+    datas = [bytes(c[2]) for c in calls]
+    caps = [(c[3] if len(c) > 3 and c[3] is not None else (len(d) // 10 + 1) * 2048 + len(d))
+            for c, d in zip(calls, datas)]
+    cs = (C.c_void_p * n)(*[c[0].h.value for c in calls])
+    ws = (C.c_void_p * n)(*[(c[1].h.value if c[1] is not None else None) for c in calls])
+    ins = (C.c_char_p * n)(*datas)
+    lens = (C.c_uint32 * n)(*[len(d) for d in datas])
+    outs = [np.zeros(max(1, cap), np.uint8) for cap in caps]
+    ops = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+    ocap = (C.c_uint64 * n)(*caps)
+    ol, cons = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+    st = np.zeros(n, np.int32)
+    unk = np.empty((n, UCAP), np.uint64)
+    ups = (C.c_void_p * n)(*[unk[i].ctypes.data for i in range(n)])
+    ucap = (C.c_uint32 * n)(*([UCAP] * n))
+    nunk, ne = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    ext = np.zeros((n, ECAP), np.uint64)
+    eps = (C.c_void_p * n)(*[ext[i].ctypes.data for i in range(n)])
+    ecap = (C.c_uint32 * n)(*([ECAP] * n))
+    rcs = (C.c_int * n)()
+    _check(lib().xcg_decode_call_many(cs, ws, ins, lens, ops, ocap, n, ol.ctypes.data, cons.ctypes.data,
+                                      st.ctypes.data, ups, ucap, nunk.ctypes.data,
+                                      eps if want_extracts else None, ecap if want_extracts else None,
+                                      ne.ctypes.data if want_extracts else None, rcs))
+    res = []
+    for i in range(n):
+        hashes = None
+        if want_extracts and int(ne[i]) != 0xFFFFFFFF:
+            hashes = [int(h) for h in ext[i, :int(ne[i])]]
+        k = min(int(ol[i]), caps[i]) if rcs[i] == 0 else 0
+        res.append((int(rcs[i]), int(st[i]), outs[i][:k].tobytes(), int(cons[i]),
+                    [int(u) for u in unk[i, :int(nunk[i])]], hashes))
+    if out_lens is not None:
+        out_lens[:] = [int(v) for v in ol]
+    return res
+
+
+def debug_decode_call_many():
+    """(launches, calls the kernel finished, calls served outside the launch) of
+    xcg_decode_call_many in this process."""
+    o = (C.c_uint64 * 3)()
+    lib().xcg_debug_decode_call_many(o)
+    return int(o[0]), int(o[1]), int(o[2])
+
+
+def pipe_debug_decode_peers():
+    """(launches, pipes in them): the xcg_decode_call_many calls
+    xcg_pipe_decoder_consume_many has made in this process."""
+    o = (C.c_uint64 * 2)()
+    lib().xcg_pipe_debug_decode_peers(o)
+    return int(o[0]), int(o[1])
 
 
 def ctx_connect(parent: Context, uuid: bytes):
