@@ -618,7 +618,8 @@ int xcg_decode_host(xcg_ctx *ctx, const uint8_t *h_enc, uint64_t enc_len, const 
  * XCG_EINVAL, before anything changes: a null pointer, n_windows == 0 or above
  * XCG_DECODE_WINDOWS_MAX, h_chunk_window[i] >= n_windows, a null window, a
  * window listed twice or of another device.  XCG_ENOTSUP on bounded and pair
- * contexts.  n == 0: XCG_OK.  The context's current window
+ * contexts: those have xcg_decode_batch_windows_bounded below, whose contract
+ * differs (it may refuse a whole batch).  n == 0: XCG_OK.  The context's current window
  * (xcg_decode_set_window) is neither used nor changed.  The call keeps 4 KiB
  * of device scratch per window on the context. */
 #define XCG_DECODE_WINDOWS_MAX 65536u
@@ -634,6 +635,50 @@ int xcg_decode_host_windows(xcg_ctx *ctx, const uint8_t *h_enc, uint64_t enc_len
                             uint32_t n_windows, const uint32_t *h_chunk_window, uint8_t *h_out, uint64_t out_cap,
                             uint64_t *h_out_off, uint64_t *h_out_len, int32_t *h_chunk_status,
                             uint64_t *h_consumed, uint32_t *h_stop_chunk, uint64_t *h_total_out);
+
+/* xcg_decode_batch_windows on a BOUNDED or PAIR context (a memory cache with a
+ * limit, or that over a disk: what every codec of the shipped wanproxy.conf
+ * has).  Arguments, outputs, statuses (0 / 1 / 3 / -1 / 2), the one stop point
+ * and *h_stop_chunk, packed outputs and XCG_EOVERFLOW with nothing written,
+ * and the windows' cursors are that call's.
+ *
+ * The cache sees the chunks as the serial loop of decode() calls would make
+ * them, in batch order across the windows: an EXTRACT or REF of chunk i sees
+ * every enter, LRU refresh, eviction, promotion and disk write of the chunks
+ * before it, whichever window they name -- one decoder's EXTRACT can evict the
+ * entry another decoder's later REF names, and that REF is then the stop.  A
+ * BACKREF reads its own window's slot whatever became of the hash in the cache.
+ *
+ * decode_skim's set is not produced, and here that also means that no op
+ * behind the stop point (of either kind) makes a lookup: nothing is refreshed,
+ * promoted or evicted there.  Present the rest of the stopped chunk to
+ * xcg_decode_batch on its window: that call blocks on its first op and does
+ * the skim with its cache effects, and the two calls together are the
+ * reference's one decode() (a lookup that misses changes nothing).
+ *
+ * XCG_ENOTSUP, with the cache, the windows and the outputs untouched -- split
+ * the batch, down to single chunks through xcg_decode_batch: what
+ * xcg_decode_batch declines on these contexts (name reuse; a hash with
+ * EXTRACTs on both sides of the stop point; more enters + lookups of
+ * persistent entries than the limit; on a pair a hash that leaves both levels
+ * before a later op names it); an unbounded context, which has
+ * xcg_decode_batch_windows.  XCG_EINVAL as in that call, and for
+ * max_chunk_len >= 2 MiB.  n == 0: XCG_OK.  The 4 KiB of device scratch per
+ * window are the same ones. */
+int xcg_decode_batch_windows_bounded(xcg_ctx *ctx, const uint8_t *d_enc, const uint64_t *d_chunk_off,
+                                     const uint32_t *d_chunk_len, uint32_t n, uint32_t max_chunk_len,
+                                     xcg_window *const *windows, uint32_t n_windows,
+                                     const uint32_t *h_chunk_window, uint8_t *d_out, uint64_t out_cap,
+                                     uint64_t *d_out_off, uint64_t *d_out_len, int32_t *d_chunk_status,
+                                     uint64_t *d_consumed, uint32_t *h_stop_chunk, uint64_t *h_total_out,
+                                     void *stream);
+/* Host-memory convenience over xcg_decode_batch_windows_bounded. */
+int xcg_decode_host_windows_bounded(xcg_ctx *ctx, const uint8_t *h_enc, uint64_t enc_len,
+                                    const uint64_t *h_chunk_off, const uint32_t *h_chunk_len, uint32_t n,
+                                    xcg_window *const *windows, uint32_t n_windows,
+                                    const uint32_t *h_chunk_window, uint8_t *h_out, uint64_t out_cap,
+                                    uint64_t *h_out_off, uint64_t *h_out_len, int32_t *h_chunk_status,
+                                    uint64_t *h_consumed, uint32_t *h_stop_chunk, uint64_t *h_total_out);
 
 /* One XCodecDecoder::decode(output, input, unknown_hashes) call from host
  * memory (xcodec/xcodec_decoder.cc:66-272), the way tack (-d, one call per
@@ -764,23 +809,31 @@ int xcg_pipe_encoder_consume_many(xcg_pipe *const *pipes, const uint8_t *const *
 /* xcg_pipe_decoder_consume for pipes[0 .. n) in order -- every out[k], every
  * rc[k] (nullable), the decoder contexts' caches and every pipe's window and
  * buffered state exactly as that loop leaves them -- with the decode() calls
- * of consecutive pipes that decode on one unbounded context made in ONE GPU
- * batch (xcg_decode_host_windows, one window per pipe), and the decode() calls
+ * of consecutive pipes that decode on one context made in ONE GPU batch
+ * (xcg_decode_host_windows, one window per pipe; on a bounded or pair context
+ * xcg_decode_host_windows_bounded, and a batch that call refuses as a whole is
+ * presented again half at a time, down to the serial call), and the decode() calls
  * of pipes that each stand alone on an unbounded context of their own -- a
  * hub's turn: many peers, a pipe each -- in ONE launch (xcg_decode_call_many,
  * a workgroup per pipe; calls of at most 1 MiB of buffered frame bytes, two or
  * more of them).  A pipe whose bytes hold a <LEARN>, a connecting pipe before
- * its <HELLO> and a pipe on a bounded or pair context are served by the serial
- * call in their place.  A pipe that fails (XCG_EPROTO) does not stop the
+ * its <HELLO> and a pipe that stands alone on a bounded or pair context are
+ * served by the serial call in their place.  A pipe that fails (XCG_EPROTO) does not stop the
  * others.  Returns the nonzero rc[k] of the lowest k; XCG_EINVAL before
  * anything changes for null arguments or a pipe listed twice; an engine
  * failure at once. */
 int xcg_pipe_decoder_consume_many(xcg_pipe *const *pipes, const uint8_t *const *data, const uint64_t *len, uint32_t n,
                                   xcg_pipe_out *out, int *rc);
-/* Diagnostics: the batched decode calls (xcg_decode_host_windows)
- * xcg_pipe_decoder_consume_many has made in this process, and the chunks (one
+/* Diagnostics: the batched decode calls (xcg_decode_host_windows and
+ * xcg_decode_host_windows_bounded) xcg_pipe_decoder_consume_many has made in this process, and the chunks (one
  * per pipe) they held. */
 void xcg_pipe_debug_decode_many(uint64_t out[2]);
+/* Diagnostics: the shortest run of pipes on a bounded or pair decoder context
+ * that xcg_pipe_decoder_consume_many takes as a batch, for both kinds (n >= 2;
+ * 0 = back to the library's measured defaults).  Returns the value set before
+ * (0 = the defaults).  Process-wide; for timing the batch against the serial
+ * loop at every run length and for tests. */
+uint32_t xcg_pipe_debug_set_run_min(uint32_t n);
 /* Diagnostics: the xcg_decode_call_many calls xcg_pipe_decoder_consume_many has
  * made in this process (one pipe per peer cache), and the pipes in them. */
 void xcg_pipe_debug_decode_peers(uint64_t out[2]);

@@ -121,9 +121,12 @@ int decode_batch_impl(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_chunk_
   return XCG_OK;
 }
 
-// xcg_decode_batch_windows without the context's completion mark.
-int decode_windows_impl(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_chunk_off, const uint32_t* d_chunk_len,
-                        uint32_t n, uint32_t max_chunk_len, xcg_window* const* windows, uint32_t n_windows,
+// xcg_decode_batch_windows (`classified` false: an unbounded context) or
+// xcg_decode_batch_windows_bounded (true: a bounded or pair context) without
+// the context's completion mark.
+int decode_windows_impl(bool classified, xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_chunk_off,
+                        const uint32_t* d_chunk_len, uint32_t n, uint32_t max_chunk_len,
+                        xcg_window* const* windows, uint32_t n_windows,
                         const uint32_t* h_chunk_window, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off,
                         uint64_t* d_out_len, int32_t* d_chunk_status, uint64_t* d_consumed, uint32_t* h_stop_chunk,
                         uint64_t* h_total_out, hipStream_t stream) {
@@ -138,7 +141,10 @@ int decode_windows_impl(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_chun
     if (windows[w]->device != c->device) return XCG_EINVAL;
   for (uint32_t i = 0; i < n; ++i)
     if (h_chunk_window[i] >= n_windows) return XCG_EINVAL;
-  if (c->bounded || c->pair) return XCG_ENOTSUP;     // (their classification caps at one window's BACKREF stop; serial calls serve them)
+  // a bounded or pair batch numbers its ops by (chunk << 21 | offset)
+  if (classified && max_chunk_len >= (1u << 21)) return XCG_EINVAL;
+  // (each kind of context has its own call: the bounded one may refuse a whole batch, this one never does)
+  if (classified != (c->bounded || c->pair != nullptr)) return XCG_ENOTSUP;
   // the plan, in the pinned block: views | chunk -> window | order | first
   const size_t nw = n_windows;
   const size_t o_cw = sizeof(xcg::WinView) * nw, o_ord = o_cw + 4ull * n, o_first = o_ord + 4ull * n,
@@ -183,16 +189,33 @@ int decode_windows_impl(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_chun
                                 d_out_off, d_out_len, d_chunk_status, d_consumed);
   a.no_window = 0;
   a.wins = &W;
+  if (c->pair) {
+    PairGpu G{};
+    G.in = d_enc; G.chunk_off = d_chunk_off;
+    G.g = c->g;
+    G.status = c->d_status;
+    if (xcg_pair_sync(c->pair, &G, stream)) return XCG_EHIP;
+  }
   uint64_t total = 0, blockp = 0, berr = 0;
   uint32_t nunk = 0;                                 // (how many hashes are unknown does not matter here)
   const int lrc = xcg_launch_decode(&a, &total, &blockp, &berr, &nunk, stream);
   if (h_total_out) *h_total_out = total;
-  if (lrc != 0) return status_of(lrc);               // (XCG_RC_HIP or _OVERFLOW: nothing was written)
+  if (lrc != 0) return status_of(lrc);               // (XCG_RC_HIP, _OVERFLOW or _NOTSUP: nothing was written)
   uint64_t* h_tend = (uint64_t*)(hm + up);
+  if (classified) *c->h_status = 0;
   if (hipMemcpyAsync(h_tend, W.w_tend, 8 * nw, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+      (classified && hipMemcpyAsync(c->h_status, c->d_status, 4, hipMemcpyDeviceToHost, stream) != hipSuccess) ||
       hipStreamSynchronize(stream) != hipSuccess)
     return XCG_EHIP;
   for (uint32_t w = 0; w < n_windows; ++w) windows[w]->count += h_tend[w];   // each decoder's cursor advances
+  // Bit 9 this late would be dec_replace_kernel's: two EXTRACTs of one hash with
+  // different bytes.  dec_dup_kernel refuses those before anything is written,
+  // so it cannot be set here; if it is, the batch is committed and the call must
+  // not report the refusal that changes nothing.
+  if (classified && (*c->h_status & (1 << 9))) {
+    (void)hipMemsetAsync(c->d_status, 0, 4, stream);
+    return XCG_EHIP;
+  }
   const uint64_t stop = blockp < berr ? blockp : berr;
   if (h_stop_chunk) *h_stop_chunk = stop == ~0ull ? n : (uint32_t)(stop >> 32);
   return XCG_OK;
@@ -221,7 +244,7 @@ int xcg_decode_batch_windows(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d
                              uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off, uint64_t* d_out_len,
                              int32_t* d_chunk_status, uint64_t* d_consumed, uint32_t* h_stop_chunk,
                              uint64_t* h_total_out, void* stream) {
-  const int rc = decode_windows_impl(c, d_enc, d_chunk_off, d_chunk_len, n, max_chunk_len, windows, n_windows,
+  const int rc = decode_windows_impl(false, c, d_enc, d_chunk_off, d_chunk_len, n, max_chunk_len, windows, n_windows,
                                      h_chunk_window, d_out, out_cap, d_out_off, d_out_len, d_chunk_status,
                                      d_consumed, h_stop_chunk, h_total_out, (hipStream_t)stream);
   if (c) {
@@ -231,8 +254,29 @@ int xcg_decode_batch_windows(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d
   return rc;
 }
 
-int xcg_decode_host_windows(xcg_ctx* c, const uint8_t* h_enc, uint64_t enc_len, const uint64_t* h_chunk_off,
-                            const uint32_t* h_chunk_len, uint32_t n, xcg_window* const* windows, uint32_t n_windows,
+int xcg_decode_batch_windows_bounded(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_chunk_off,
+                                     const uint32_t* d_chunk_len, uint32_t n, uint32_t max_chunk_len,
+                             xcg_window* const* windows, uint32_t n_windows, const uint32_t* h_chunk_window,
+                             uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off, uint64_t* d_out_len,
+                             int32_t* d_chunk_status, uint64_t* d_consumed, uint32_t* h_stop_chunk,
+                             uint64_t* h_total_out, void* stream) {
+  const int rc = decode_windows_impl(true, c, d_enc, d_chunk_off, d_chunk_len, n, max_chunk_len, windows, n_windows,
+                                     h_chunk_window, d_out, out_cap, d_out_off, d_out_len, d_chunk_status,
+                                     d_consumed, h_stop_chunk, h_total_out, (hipStream_t)stream);
+  if (c) {
+    DeviceGuard g(c->device);
+    ctx_mark(c, (hipStream_t)stream);
+  }
+  return rc;
+}
+
+}  // extern "C"
+
+namespace {
+// xcg_decode_host_windows / _bounded: staging around the device call.
+int decode_host_windows_impl(bool classified, xcg_ctx* c, const uint8_t* h_enc, uint64_t enc_len,
+                             const uint64_t* h_chunk_off, const uint32_t* h_chunk_len, uint32_t n,
+                             xcg_window* const* windows, uint32_t n_windows,
                             const uint32_t* h_chunk_window, uint8_t* h_out, uint64_t out_cap, uint64_t* h_out_off,
                             uint64_t* h_out_len, int32_t* h_chunk_status, uint64_t* h_consumed,
                             uint32_t* h_stop_chunk, uint64_t* h_total_out) {
@@ -266,9 +310,9 @@ int xcg_decode_host_windows(xcg_ctx* c, const uint8_t* h_enc, uint64_t enc_len, 
   uint8_t* d_out = dm + meta + inb;
   if (hipMemcpyAsync(dm, hm, meta + enc_len, hipMemcpyHostToDevice, st) != hipSuccess) return XCG_EHIP;
   uint64_t total = 0;
-  rc = xcg_decode_batch_windows(c, dm + meta, (const uint64_t*)dm, (const uint32_t*)(dm + 32ull * n), n, maxlen,
-                                windows, n_windows, h_chunk_window, d_out, out_cap, d_oo, d_ol, d_st, d_cons,
-                                h_stop_chunk, &total, st);
+  const auto call = classified ? xcg_decode_batch_windows_bounded : xcg_decode_batch_windows;
+  rc = call(c, dm + meta, (const uint64_t*)dm, (const uint32_t*)(dm + 32ull * n), n, maxlen, windows, n_windows,
+            h_chunk_window, d_out, out_cap, d_oo, d_ol, d_st, d_cons, h_stop_chunk, &total, st);
   if (h_total_out) *h_total_out = total;
   if (rc != XCG_OK) return rc;
   uint8_t* ho = hm + meta + inb;
@@ -284,6 +328,30 @@ int xcg_decode_host_windows(xcg_ctx* c, const uint8_t* h_enc, uint64_t enc_len, 
   memcpy(h_chunk_status, hm + 36ull * n, 4ull * n);
   if (nout) memcpy(h_out, ho, nout);
   return XCG_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int xcg_decode_host_windows(xcg_ctx* c, const uint8_t* h_enc, uint64_t enc_len, const uint64_t* h_chunk_off,
+                            const uint32_t* h_chunk_len, uint32_t n, xcg_window* const* windows, uint32_t n_windows,
+                            const uint32_t* h_chunk_window, uint8_t* h_out, uint64_t out_cap, uint64_t* h_out_off,
+                            uint64_t* h_out_len, int32_t* h_chunk_status, uint64_t* h_consumed,
+                            uint32_t* h_stop_chunk, uint64_t* h_total_out) {
+  return decode_host_windows_impl(false, c, h_enc, enc_len, h_chunk_off, h_chunk_len, n, windows, n_windows,
+                                  h_chunk_window, h_out, out_cap, h_out_off, h_out_len, h_chunk_status, h_consumed,
+                                  h_stop_chunk, h_total_out);
+}
+
+int xcg_decode_host_windows_bounded(xcg_ctx* c, const uint8_t* h_enc, uint64_t enc_len,
+                                    const uint64_t* h_chunk_off, const uint32_t* h_chunk_len, uint32_t n,
+                                    xcg_window* const* windows, uint32_t n_windows, const uint32_t* h_chunk_window,
+                                    uint8_t* h_out, uint64_t out_cap, uint64_t* h_out_off, uint64_t* h_out_len,
+                                    int32_t* h_chunk_status, uint64_t* h_consumed, uint32_t* h_stop_chunk,
+                                    uint64_t* h_total_out) {
+  return decode_host_windows_impl(true, c, h_enc, enc_len, h_chunk_off, h_chunk_len, n, windows, n_windows,
+                                  h_chunk_window, h_out, out_cap, h_out_off, h_out_len, h_chunk_status, h_consumed,
+                                  h_stop_chunk, h_total_out);
 }
 
 int xcg_decode_batch_independent(xcg_ctx* c, const uint8_t* d_enc, const uint64_t* d_chunk_off,

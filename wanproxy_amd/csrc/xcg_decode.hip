@@ -626,6 +626,7 @@ xcg::DecParams dec_params(const XcgDecodeArgs* a) {
   p.n_bref = a->chunk_tmp + n;
   p.decl_base = a->chunk_tmp + 2ull * n;
   p.n_decl_emit = a->chunk_tmp + 3ull * n;
+  p.op_base = p.decl_base;
   p.win_hash = a->win_hash;
   p.win_seg = a->win_seg;
   p.win_count = a->win_count;
@@ -637,7 +638,8 @@ xcg::DecParams dec_params(const XcgDecodeArgs* a) {
   return p;
 }
 
-// The one-window record pass over every declare and the BACKREF check, as the
+// The record pass over every declare and the BACKREF check (one window, or one
+// per decoder when p.wins is set), as the
 // classified path launches them ahead of its classification.  Defined behind
 // xcg_launch_decode: the kernels are instantiated, and so laid out in the code
 // object, in the order of their first use, and the paths that launch what they
@@ -673,7 +675,11 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
     return XCG_RC_HIP;
   // scan, then number the declares
   hipLaunchKernelGGL(decode_kernel<false>, grid, block, 0, stream, p);
-  if (a->wins) dec_windows_number(a->wins, p, &d->n_decl, stream);   // (per window)
+  const bool classified = a->lru != nullptr || a->pair != nullptr;
+  if (a->wins) {
+    dec_windows_number(a->wins, p, &d->n_decl, stream);     // (per window)
+    if (classified) p.op_base = dec_windows_op_base(a->wins, p, &d->n_decl, stream);   // (the op list stays in batch order)
+  }
   else hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, stream, (const uint64_t*)p.n_decl,
                           (uint64_t*)p.decl_base, n, &d->n_decl);
   hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, stream, (const uint64_t*)p.n_bref,
@@ -688,7 +694,6 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
   // The count of flagged hashes comes back with the sizing pass's readback.
   if (ndup > a->dup_cap) return XCG_RC_HIP;                  // (the list holds every EXTRACT the batch can have)
   h->reuse[0] = ndup;
-  const bool classified = a->lru != nullptr || a->pair != nullptr;
   if (ndup) {
     if (hipMemsetAsync(a->x_flag, 0, 4ull * (a->x_mask + 1), stream) != hipSuccess) return XCG_RC_HIP;
     hipLaunchKernelGGL(dec_dup_kernel, dim3((unsigned)((ndup + 3) / 4)), dim3(256), 0, stream, p, (uint32_t)ndup,
@@ -841,9 +846,11 @@ extern "C" int xcg_launch_decode(const XcgDecodeArgs* a, uint64_t* total_out, ui
 
 namespace {
 void dec_launch_records(const xcg::DecParams& p, uint64_t ndecl, hipStream_t stream) {
-  hipLaunchKernelGGL(xcg::decl_record_kernel<false>, dim3((p.n + 3) / 4), dim3(256), 0, stream, p, ndecl);
+  if (p.wins) xcg::dec_windows_records(p, false, stream);
+  else hipLaunchKernelGGL(xcg::decl_record_kernel<false>, dim3((p.n + 3) / 4), dim3(256), 0, stream, p, ndecl);
 }
 void dec_launch_brefcheck(const xcg::DecParams& p, hipStream_t stream) {
-  hipLaunchKernelGGL(xcg::decode_brefcheck_kernel<false>, dim3((p.n + 3) / 4), dim3(256), 0, stream, p);
+  if (p.wins) hipLaunchKernelGGL(xcg::decode_brefcheck_kernel<true>, dim3((p.n + 3) / 4), dim3(256), 0, stream, p);
+  else hipLaunchKernelGGL(xcg::decode_brefcheck_kernel<false>, dim3((p.n + 3) / 4), dim3(256), 0, stream, p);
 }
 }  // namespace

@@ -75,6 +75,11 @@ struct DecParams {
   WinView* wins;               // [n_windows]
   const uint32_t* chunk_win;   // chunk -> window
   uint64_t* w_tend;            // [n_windows] declares of each window before the stop point
+  // ---- bounded cache or pair: the chunk's first op in the batch-order op list
+  // (raw[] / ev[]): an exclusive scan of n_decl in chunk order.  One window:
+  // decl_base itself; several: their own scan (dec_windows_op_base), since a
+  // window-relative base is not unique across windows.
+  const uint64_t* op_base;
 };
 
 // One decoder's window for the kernels that take several: hash[256], seg[256 *
@@ -436,6 +441,12 @@ int dec_classified_commit(const XcgDecodeArgs* a, const DecParams& p, const DecC
 // into p.decl_base (each chunk's base within its own window), every window's
 // first and total, the batch's total into *d_total.
 void dec_windows_number(const XcgDecodeWindows* w, const DecParams& p, uint64_t* d_total, hipStream_t stream);
+// Behind the numbering (bounded and pair contexts): p.n_decl scanned in chunk
+// order, the op list's base of every chunk (DecParams::op_base), into the
+// numbering's scan scratch, which it no longer needs.  *d_total gets the same
+// total again.
+const uint64_t* dec_windows_op_base(const XcgDecodeWindows* w, const DecParams& p, uint64_t* d_total,
+                                    hipStream_t stream);
 // Records of every declare, window-major (the batch holds BACKREFs).
 void dec_windows_records(const DecParams& p, bool reuse, hipStream_t stream);
 // After the emit pass: every window's t_end, (tail: p.D = the 256 records per

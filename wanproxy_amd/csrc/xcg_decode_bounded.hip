@@ -14,14 +14,15 @@
 namespace xcg {
 
 // Every EXTRACT / REF op of the batch as (lo, hi, op offset, op), packed by
-// chunk at decl_base[c] (the scan's declare numbering).  One wave per chunk.
+// chunk at op_base[c] (the scan's declare numbering in chunk order).  One wave
+// per chunk.
 __global__ __launch_bounds__(256) void dec_ops_kernel(DecParams prm, uint4* raw) {
   const int wv = (int)readfirst(threadIdx.x >> 6);
   const uint32_t chunk = blockIdx.x * 4u + (uint32_t)wv;
   if (chunk >= prm.n) return;
   const uint8_t* x = prm.in + prm.chunk_off[chunk];
   const uint32_t len = prm.chunk_len[chunk];
-  uint64_t t = prm.decl_base[chunk];
+  uint64_t t = prm.op_base[chunk];
   walk_op_headers(
       x, len, chunk,
       [&](uint32_t i) {
@@ -45,7 +46,7 @@ __global__ __launch_bounds__(256) void dec_ops_kernel(DecParams prm, uint4* raw)
 // REF (:141-163) hits likewise or is unknown -- the stream stops at the first
 // one.  After the stop point decode_skim (:196-272) still looks up every REF
 // (a hit refreshes the entry) against the cache as it stands there.
-// ev[decl_base[c] + k]: (lo, hi, op offset, kind << 30 | ref) with GMISS =
+// ev[op_base[c] + k]: (lo, hi, op offset, kind << 30 | ref) with GMISS =
 // no cache effect; ENTERs also as declaration rows.  One wave per chunk.
 //
 // PAIR (XCodecCachePair, xcg_pair.hip): ptime is the time a hash leaves both
@@ -61,18 +62,23 @@ __global__ __launch_bounds__(256) void dec_ops_kernel(DecParams prm, uint4* raw)
 // no unknown REF stands in front of it, every op behind it is GMISS and an
 // unknown REF there is not one.  With the unknown-REF stop in front, the skim
 // runs on over the BACKREFs (:261-266) and the cap means nothing.
+//
+// `noskim` (several windows, xcg_decode_batch_windows_bounded): the call ends
+// at its stop point whichever kind it is and leaves the skim to the caller's
+// next call, so every op behind min(blockp, cap) is GMISS.
 template <bool PAIR>
 __global__ __launch_bounds__(256) void dec_classify_kernel(DecParams prm, const uint4* raw, uint4* ev, uint32_t* nev,
                                                            uint4* drow, uint32_t* ndecl, uint32_t maxd,
                                                            uint64_t blockp, uint64_t* block_new, uint32_t* changes,
-                                                           int first) {
+                                                           int first, int noskim) {
   const uint32_t c = blockIdx.x * 4u + (uint32_t)readfirst(threadIdx.x >> 6);
   if (c >= prm.n) return;
   const uint32_t cnt = (uint32_t)prm.n_decl[c];
-  const uint64_t base = prm.decl_base[c];
+  const uint64_t base = prm.op_base[c];
   const uint64_t tb = blockp == ~0ull ? ~0ull : ((blockp >> 32 << 21) | (uint32_t)blockp);
   const uint64_t cap = readfirst64(*prm.berr_pos);
   const bool capped = cap < blockp;                   // the error stop comes first
+  const uint64_t lim = noskim ? min(cap, blockp) : capped ? cap : ~0ull;   // ops behind it: no cache effect
   const uint8_t* x = prm.in + prm.chunk_off[c];
   uint32_t nd = 0;
   bool chg = false;
@@ -83,7 +89,7 @@ __global__ __launch_bounds__(256) void dec_classify_kernel(DecParams prm, const 
     const uint64_t here = spos(c, r.z), t = ((uint64_t)c << 21) | r.z;
     uint32_t kind = EV_GMISS, ref = 0, zflag = 0;
     bool enter = false;
-    if (valid && !(capped && here > cap)) {
+    if (valid && here <= lim) {
       const uint64_t e = tab_lookup_t(prm.x, r.x, r.y);
       if (here <= blockp) {                           // (the op at the stop point is looked at again)
         if (e != ~0ull && e < here) {
@@ -157,7 +163,7 @@ __global__ __launch_bounds__(256) void dec_replace_kernel(DecParams prm, const u
   const uint32_t c = blockIdx.x * 4u + (uint32_t)readfirst(threadIdx.x >> 6);
   if (c >= prm.n) return;
   const uint32_t cnt = (uint32_t)prm.n_decl[c];
-  const uint64_t base = prm.decl_base[c];
+  const uint64_t base = prm.op_base[c];
   const uint8_t* x = prm.in + prm.chunk_off[c];
   for (uint32_t k = 0; k < cnt; ++k) {
     const uint4 e = ev[base + k];
@@ -230,7 +236,8 @@ int classify_passes(const XcgDecodeArgs* a, const DecParams& p, const DecClassif
         hipMemsetAsync(&cw->changes, 0, 4, stream) != hipSuccess)
       return XCG_RC_HIP;
     hipLaunchKernelGGL(dec_classify_kernel<PAIR>, grid, block, 0, stream, p, (const uint4*)K.raw, K.evs, K.nev, K.rows,
-                       K.nrows, a->maxd, blockp, &cw->block, &cw->changes, PAIR || pass == 0 ? 1 : 0);
+                       K.nrows, a->maxd, blockp, &cw->block, &cw->changes, PAIR || pass == 0 ? 1 : 0,
+                       a->wins != nullptr ? 1 : 0);
     bool same = false;
     const int rc = step(pass, blockp, &same);
     if (rc) return rc;
@@ -287,7 +294,7 @@ int dec_classify(const XcgDecodeArgs* a, DecParams& p, uint64_t ndecl, StreamTem
       if (hipMemcpyAsync(&h->cls, cw, 8, hipMemcpyDeviceToHost, stream) != hipSuccess) return (int)XCG_RC_HIP;
       int same = 0;
       const PairGpu G = pair_gpu(a, K->rows);
-      const int prc = xcg_pair_decode_pass(a->pair, &G, K->evs, p.decl_base, p.n_decl, n, ndecl, a->maxd, &same, stream);
+      const int prc = xcg_pair_decode_pass(a->pair, &G, K->evs, p.op_base, p.n_decl, n, ndecl, a->maxd, &same, stream);
       if (prc) return prc;
       if (getenv("XCG_PAIR_DEBUG"))
         fprintf(stderr, "pair-dec: n %u pass %d same %d block %llx -> %llx\n", n, pass, same,

@@ -22,6 +22,11 @@
 //   update  window_update_kernel's step over (window, slot); a window the
 //           batch did not declare into is not touched
 //
+// On a bounded or pair context (xcg_decode_batch_windows_bounded) the
+// classified passes of xcg_decode_bounded.hip index their op list in batch
+// order, not by window: dec_windows_op_base scans the declare counts once more,
+// in chunk order, for them.
+//
 // The emit and BACKREF-check kernels are xcg_decode.hip's, instantiated with
 // WINS: their BACKREFs read the chunk's ManyWindow through window_slot_of
 // (xcg_decode_batch.h) instead of the one window through window_slot.
@@ -144,6 +149,12 @@ void dec_windows_number(const XcgDecodeWindows* w, const DecParams& p, uint64_t*
                      n, nw, p.wins);
   hipLaunchKernelGGL(win_base_kernel, gn, block, 0, stream, (const uint64_t*)base, w->order, w->chunk_win,
                      (const WinView*)p.wins, n, (uint64_t*)p.decl_base);
+}
+
+const uint64_t* dec_windows_op_base(const XcgDecodeWindows* w, const DecParams& p, uint64_t* d_total,
+                                    hipStream_t stream) {
+  xcg_launch_exclusive_scan((const uint64_t*)p.n_decl, w->scan_tmp, p.n, d_total, stream);
+  return w->scan_tmp;
 }
 
 void dec_windows_records(const DecParams& p, bool reuse, hipStream_t stream) {

@@ -16,7 +16,8 @@
 // an encoder context (one codec, one cache) can be encoded in one GPU batch
 // (xcg_pipe_encoder_consume_many), and pipes that share a decoder context (one
 // peer's cache) decoded in one (xcg_pipe_decoder_consume_many, over
-// xcg_decode_host_windows: one BACKREF window per pipe; pipes that each stand
+// xcg_decode_host_windows, or xcg_decode_host_windows_bounded on a bounded or
+// pair context: one BACKREF window per pipe; pipes that each stand
 // alone on a peer's cache in one launch, xcg_decode_call_many), both in the order the
 // reference's single event thread would have served them.  The encoder side is
 // two halves the codec layer shares (xcg_pipe_step.h, xcg_codec.cpp): the
@@ -398,9 +399,23 @@ std::atomic<uint64_t> g_peer_calls{0}, g_peer_pipes{0};
 constexpr uint32_t PEERS_MIN = 2;
 constexpr size_t PEERS_MAX_CALL = 1u << 20;              // what xcg_decode_call_many decodes in its launch
 
+// The shortest run on a bounded or on a pair context that goes up as a batch
+// (xcg_decode_host_windows_bounded); shorter runs are the serial calls.
+// (Measured: scripts/pipe_decode_many_time.py --cache bounded|pair,
+// profiles/pipe_decode_many_bounded.txt; the rule and the numbers are in
+// DESIGN.md section 9 item 4.)  xcg_pipe_debug_set_run_min overrides both, for
+// that measurement and for tests of the batch at run lengths below them.
+constexpr uint32_t BOUNDED_RUN_MIN = 2, PAIR_RUN_MIN = 2;
+std::atomic<uint32_t> g_run_min{0};                      // (0: the constants)
+uint32_t classified_run_min(const xcg_ctx* c) {
+  const uint32_t set = g_run_min.load();
+  if (set >= 2) return set;
+  return xcg_pair_xuid(c) >= 0 ? PAIR_RUN_MIN : BOUNDED_RUN_MIN;
+}
+
 // A pipe xcg_pipe_decoder_consume_many may take into a run (see there).
 bool plain(const xcg_pipe* p, const uint8_t* data, uint64_t len) {
-  if (!p->dec || !xcg_ctx_unbounded(p->dec)) return false;
+  if (!p->dec) return false;
   if (len == 0) return true;                             // (peer closed: no byte is looked at)
   if (p->dbuf.empty()) return !reaches_learn(data, len);
   std::vector<uint8_t> all(p->dbuf);
@@ -618,8 +633,9 @@ int xcg_pipe_decoder_consume(xcg_pipe* p, const uint8_t* data, uint64_t len, xcg
 // consecutive pipes on one decoder context in one GPU batch.
 //
 // A pipe is *plain* when its pending wire bytes hold no <LEARN>, it decodes on
-// a context it has already (a connecting pipe past its <HELLO>) and that
-// context is unbounded: its decode_ops touches no cache, so it can run before
+// a context it has already (a connecting pipe past its <HELLO>): its
+// decode_ops touches no decoder cache (only a <LEARN> enters one there), so it
+// can run before
 // the pipes in front of it have decoded.  A run is a maximal sequence of
 // consecutive plain pipes on one context; each of its pipes brings at most one
 // chunk, its frame buffer, and the run is one xcg_decode_host_windows call over
@@ -628,6 +644,14 @@ int xcg_pipe_decoder_consume(xcg_pipe* p, const uint8_t* data, uint64_t len, xcg
 // the single call once more for decode_skim's set (that call blocks on its
 // first op: it consumes and declares nothing), and the pipes behind it are
 // the next batch.  Every other pipe is the serial call.
+//
+// On a bounded or pair context the batch is xcg_decode_host_windows_bounded,
+// for runs of classified_run_min() pipes or more (shorter ones, a run of one
+// included, are the serial calls).  That call may refuse a batch as a whole
+// (XCG_ENOTSUP, nothing changed): the first half of the pending pipes is then
+// presented again, down to a single pipe by decode_data().  The call makes no
+// lookup behind its stop point, and the stopped pipe's decode_data() -- which
+// blocks on its first op -- does the skim with its cache effects.
 //
 // A run of ONE -- a hub's turn: many peers, a pipe each -- runs its ops at once
 // and, if that leaves frame bytes to decode (no unknown hash outstanding, at
@@ -740,6 +764,11 @@ int xcg_pipe_decoder_consume_many(xcg_pipe* const* pipes, const uint8_t* const* 
     }
     uint32_t e = k;
     while (e < n && pipes[e]->dec == ctx && plain(pipes[e], data[e], len[e])) ++e;
+    const bool classified = ctx && !xcg_ctx_unbounded(ctx);
+    if (classified && e > k && e - k < classified_run_min(ctx)) {   // (the held path is the unbounded contexts')
+      for (; k < e; ++k) serial(k);
+      continue;
+    }
     if (e - k == 1) {
       // a run of one: its ops now; its decode() joins the held set
       xcg_pipe* p = pipes[k];
@@ -791,14 +820,17 @@ int xcg_pipe_decoder_consume_many(xcg_pipe* const* pipes, const uint8_t* const* 
       p->settle(rc);
       done(j, rc);
     }
+    uint32_t take = (uint32_t)pending.size();             // (less after a refusal: the first half again)
     while (!pending.empty()) {
-      const uint32_t m = (uint32_t)pending.size();
+      const uint32_t m = take;
       if (m == 1) {                                      // the single call
         xcg_pipe* p = pipes[pending[0]];
         const int rc = p->decode_data();
         p->settle(rc);
         done(pending[0], rc);
-        break;
+        pending.erase(pending.begin());
+        take = (uint32_t)pending.size();
+        continue;
       }
       std::vector<uint64_t> off(m), oo(m), ol(m), cons(m);
       std::vector<uint32_t> cl(m), cw(m);
@@ -818,9 +850,13 @@ int xcg_pipe_decoder_consume_many(xcg_pipe* const* pipes, const uint8_t* const* 
       for (uint32_t i = 0; i < m; ++i) memcpy(in.data() + off[i], pipes[pending[i]]->fbuf.data(), cl[i]);
       std::unique_ptr<uint8_t[]> dout(new uint8_t[cap]);
       uint32_t stop = m;
-      const int brc = xcg_decode_host_windows(ctx, in.data(), total, off.data(), cl.data(), m, wins.data(), m,
-                                              cw.data(), dout.get(), cap, oo.data(), ol.data(), st.data(),
-                                              cons.data(), &stop, nullptr);
+      const auto call = classified ? xcg_decode_host_windows_bounded : xcg_decode_host_windows;
+      const int brc = call(ctx, in.data(), total, off.data(), cl.data(), m, wins.data(), m, cw.data(), dout.get(), cap,
+                           oo.data(), ol.data(), st.data(), cons.data(), &stop, nullptr);
+      if (classified && brc == XCG_ENOTSUP) {            // refused as a whole: nothing has changed
+        take = m / 2;
+        continue;
+      }
       if (brc != XCG_OK) return brc;                     // an engine failure: at once
       ++g_many_calls;
       g_many_chunks += m;
@@ -833,6 +869,7 @@ int xcg_pipe_decoder_consume_many(xcg_pipe* const* pipes, const uint8_t* const* 
         done(pending[i], rc);
       }
       pending.erase(pending.begin(), pending.begin() + upto);
+      take = (uint32_t)pending.size();
     }
     k = e;
   }
@@ -845,6 +882,8 @@ void xcg_pipe_debug_decode_many(uint64_t out[2]) {
   out[0] = g_many_calls;
   out[1] = g_many_chunks;
 }
+
+uint32_t xcg_pipe_debug_set_run_min(uint32_t n) { return g_run_min.exchange(n >= 2 ? n : 0u); }
 
 void xcg_pipe_debug_decode_peers(uint64_t out[2]) {
   out[0] = g_peer_calls;

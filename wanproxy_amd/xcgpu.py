@@ -144,6 +144,11 @@ def lib():
         L.xcg_decode_host_windows.argtypes = [vp, u8p, C.c_uint64, u64p, u32p, C.c_uint32, vp, C.c_uint32, vp, u8p,
                                               C.c_uint64, u64p, u64p, vp, u64p, vp, vp]
         L.xcg_decode_host_windows.restype = C.c_int
+    if hasattr(L, 'xcg_decode_batch_windows_bounded'):   # (likewise: a build from before the bounded windows call)
+        L.xcg_decode_batch_windows_bounded.argtypes = L.xcg_decode_batch_windows.argtypes
+        L.xcg_decode_batch_windows_bounded.restype = C.c_int
+        L.xcg_decode_host_windows_bounded.argtypes = L.xcg_decode_host_windows.argtypes
+        L.xcg_decode_host_windows_bounded.restype = C.c_int
     L.xcg_decode_batch_independent.argtypes = [vp, u8p, u64p, u32p, C.c_uint32, C.c_uint32, u8p, u64p, u64p, u64p, vp,
                                                u64p, u64p, vp]
     L.xcg_decode_batch_independent.restype = C.c_int
@@ -626,6 +631,18 @@ class Context:
         and BACKREFs from windows[chunk_window[i]] (Window objects).  Returns
         (outs, status, consumed, stop_chunk) -- see xcg_decode_batch_windows;
         host=True goes through xcg_decode_host_windows."""
+        return self._decode_chunks_windows(chunks, windows, chunk_window, host, False)
+
+    def decode_chunks_windows_bounded(self, chunks, windows, chunk_window, host: bool = False):
+        """decode_chunks_windows on a bounded or pair context
+        (xcg_decode_batch_windows_bounded / xcg_decode_host_windows_bounded):
+        the same arguments and return shape; XcgError(-95) when the batch is
+        refused as a whole (nothing has changed: split it)."""
+        return self._decode_chunks_windows(chunks, windows, chunk_window, host, True)
+
+    def _decode_chunks_windows(self, chunks, windows, chunk_window, host, bounded):
+        host_call = lib().xcg_decode_host_windows_bounded if bounded else lib().xcg_decode_host_windows
+        batch_call = lib().xcg_decode_batch_windows_bounded if bounded else lib().xcg_decode_batch_windows
         n = len(chunks)
         lens = np.array([len(e) for e in chunks], dtype=np.uint32)
         offs = np.zeros(n, dtype=np.uint64)
@@ -644,7 +661,7 @@ class Context:
             st = np.zeros(n, dtype=np.int32)
             for _ in range(2):
                 out = np.zeros(cap, dtype=np.uint8)
-                rc = lib().xcg_decode_host_windows(
+                rc = host_call(
                     self.h, blob.ctypes.data, sum(len(e) for e in chunks), offs.ctypes.data, lens.ctypes.data, n,
                     wins, len(windows), cw.ctypes.data, out.ctypes.data, cap, oo.ctypes.data, ol.ctypes.data,
                     st.ctypes.data, cons.ctypes.data, stop.ctypes.data, total.ctypes.data)
@@ -664,7 +681,7 @@ class Context:
             d_cons = torch.zeros(n, dtype=torch.int64, device=dev)
             for _ in range(2):
                 d_out = torch.zeros(cap, dtype=torch.uint8, device=dev)
-                rc = lib().xcg_decode_batch_windows(
+                rc = batch_call(
                     self.h, C.c_void_p(d_in.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(d_len.data_ptr()),
                     n, int(lens.max()) if n else 0, wins, len(windows), cw.ctypes.data,
                     C.c_void_p(d_out.data_ptr()), cap, C.c_void_p(d_oo.data_ptr()), C.c_void_p(d_ol.data_ptr()),
@@ -1047,7 +1064,7 @@ class PipePair:
         consecutive pipes on one decoder context in one GPU batch and those of
         pipes that each stand alone on a context of their own (many peers, a
         pipe each) in one launch (xcg_pipe_decoder_consume_many:
-        xcg_decode_host_windows, xcg_decode_call_many).  One (to_peer, to_local, local_eos,
+        xcg_decode_host_windows / _bounded, xcg_decode_call_many).  One (to_peer, to_local, local_eos,
         peer_eos) per pipe, or the XCGError its serial call would have raised;
         bad arguments (a pipe listed twice) and engine failures raise."""
         n = len(pipes)
